@@ -9,12 +9,21 @@ barrier + torch.cuda.synchronize() on both sides; elapsed is the MAX over
 ranks; rank 0 prints ONE JSON line.
 
 Synthetic data (no network), random-init weights, bf16 compute on GPU.
+Model init and data are seeded per rank, so the same arguments give the same
+inputs on every run.
+
+A plain run does only what the headline figure needs: set up, capture the
+graph, warm up, time K steps, print the line. `--dump-outputs DIR` also
+writes what the last timed train_step returned (rank 0's loss, and accuracy
+for the classification tasks) as DIR/<name>.npy in float32. `--full` is where
+any measurement beyond the headline figure belongs; there is none at present.
 """
 
 from __future__ import annotations
 
 import argparse
 import json
+import os
 import time
 
 import torch
@@ -70,6 +79,21 @@ def build(task: str, device, dtype):
     return model, trainer, model_name
 
 
+_DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir: str, outputs: dict[str, torch.Tensor]) -> None:
+    """Write every tensor train_step returned as <out_dir>/<name>.npy (float32)."""
+    import numpy as np
+
+    arrays = {name: t.detach().to("cpu", torch.float32).numpy() for name, t in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= _DUMP_LIMIT_BYTES, f"step outputs are {total} bytes; sample them before dumping"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -83,6 +107,12 @@ def main() -> None:
     p.add_argument("--graph", choices=["auto", "1", "0"], default="auto",
                    help="hipGraph-capture the train step (any world size; capture "
                         "failure falls back to eager COORDINATED across ranks)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last train_step "
+                        "returned (rank 0) as DIR/<name>.npy in float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure "
+                        "(none at present: the plain run is the whole benchmark)")
     args = p.parse_args()
 
     from jimm_amd.ops._backend import maybe_enable_tunableop
@@ -148,10 +178,13 @@ def main() -> None:
         trainer.train_step(next(it))
     sync()
     t0 = time.perf_counter()
+    last = {}
     for _ in range(args.steps):
-        trainer.train_step(next(it))
+        last = trainer.train_step(next(it))
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     # MAX over ranks
     if dist.is_initialized():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if on_gpu else "cpu")

@@ -492,21 +492,29 @@ def test_comm_stats_world2():
     spawn(_comm_stats_world2, port=29527)
 
 
-def test_bench_torchrun_world2():
+def test_bench_torchrun_world2(tmp_path):
     """The driver's exact launch path: torchrun --nproc-per-node 2 bench.py
     on CPU/gloo — rendezvous on 127.0.0.1, per-rank data shards, barrier +
-    max-over-ranks timing, exactly one JSON line from rank 0."""
+    max-over-ranks timing, exactly one JSON line from rank 0; --dump-outputs
+    leaves the last step's outputs as float32 .npy files."""
     import json
     import subprocess
     import sys
 
+    import numpy as np
+
+    dump = tmp_path / "dump"
+    # CPU/gloo is the point here: hide any GPUs from the ranks, so a box with
+    # fewer devices than ranks runs the same path as one with none
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29531", "bench.py", "--gpus", "2",
-         "--steps", "2", "--warmup", "1", "--batch", "2"],
+         "--steps", "2", "--warmup", "1", "--batch", "2",
+         "--dump-outputs", str(dump)],
         capture_output=True, text=True, timeout=600,
-        cwd=os.path.join(os.path.dirname(__file__), ".."),
+        cwd=os.path.join(os.path.dirname(__file__), ".."), env=env,
     )
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -524,6 +532,13 @@ def test_bench_torchrun_world2():
         assert key in out["config"], key
     assert out["scaling"] == "weak" and out["higher_is_better"] is True
     assert out["data"] == "synthetic"
+    assert out["dtype"] == "fp32"  # the ranks really ran on CPU
+    assert sorted(f.name for f in dump.iterdir()) == ["accuracy.npy", "loss.npy"]
+    for f in dump.iterdir():
+        a = np.load(f)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), (f.name, a)
+    # random-init 1000-class cross-entropy sits near ln(1000) = 6.9
+    assert 5.0 < float(np.load(dump / "loss.npy")) < 9.0
 
 
 def test_bucket_overlap_stress():
