@@ -32,10 +32,10 @@ FLOORS_GEMM = {  # (M, N, K, act): fwd_tf
     (201728, 3072, 768, "gelu"): 600,
     (201728, 768, 3072, ""): 890,
 }
-FLOORS_DW = {  # (M, N, K): tf (post splitm rework + workspace combine)
-    (201728, 2304, 768): 640,
-    (201728, 3072, 768): 730,
-    (201728, 768, 3072): 730,
+FLOORS_DW = {  # (M, N, K): tf (staging ring + round-aware splits; 0.9 x measured 953 / 980 / 970)
+    (201728, 2304, 768): 855,
+    (201728, 3072, 768): 880,
+    (201728, 768, 3072): 870,
 }
 
 

@@ -53,8 +53,10 @@ torch::Tensor xent_rows_bwd(torch::Tensor logits, torch::Tensor labels, torch::T
 std::vector<torch::Tensor> sigmoid_loss_ew(torch::Tensor logits, int64_t diag0);
 bool gemm8p_supported(int64_t M, int64_t N, int64_t K);
 bool gemm_tn8p_supported(int64_t M, int64_t N, int64_t K);
-torch::Tensor gemm_tn_8p(torch::Tensor dz, torch::Tensor x);
-std::vector<torch::Tensor> gemm_tn_8p_db(torch::Tensor dz, torch::Tensor x);
+int64_t gemm_tn8p_choose_splitm(int64_t M, int64_t tiles, int64_t cus);
+torch::Tensor gemm_tn_8p(torch::Tensor dz, torch::Tensor x, int64_t splitm, bool out_bf16);
+std::vector<torch::Tensor> gemm_tn_8p_db(torch::Tensor dz, torch::Tensor x, int64_t splitm,
+                                         bool out_bf16);
 torch::Tensor gemm_nt_8p_gradact(torch::Tensor dy, torch::Tensor wt, torch::Tensor z, std::string act);
 torch::Tensor tr16_probe(torch::Tensor src, int64_t mode);
 std::vector<torch::Tensor> linear_fwd(torch::Tensor x, torch::Tensor w,
@@ -90,8 +92,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_supported", &gemm_supported, "MFMA GEMM shape support check");
   m.def("gemm8p_supported", &gemm8p_supported, "8-phase 256-tile GEMM shape check");
   m.def("gemm_tn8p_supported", &gemm_tn8p_supported, "TN dW GEMM shape check");
-  m.def("gemm_tn_8p", &gemm_tn_8p, "TN weight-grad GEMM, split-M, tr_b16 (K15)");
-  m.def("gemm_tn_8p_db", &gemm_tn_8p_db, "split-M TN dW with fused bias-grad colsum");
+  m.def("gemm_tn8p_choose_splitm", &gemm_tn8p_choose_splitm,
+        "TN dW split-M heuristic (host only)", py::arg("M"), py::arg("tiles"), py::arg("cus"));
+  m.def("gemm_tn_8p", &gemm_tn_8p, "TN weight-grad GEMM, split-M, tr_b16 (K15)",
+        py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false);
+  m.def("gemm_tn_8p_db", &gemm_tn_8p_db, "split-M TN dW with fused bias-grad colsum",
+        py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false);
   m.def("gemm_nt_8p_gradact", &gemm_nt_8p_gradact, "dX GEMM with fused act-backward epilogue");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 lane-mapping probe");
   m.def("l2norm_fwd", &l2norm_fwd, "row L2-normalize forward (K12)");

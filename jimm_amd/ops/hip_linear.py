@@ -96,7 +96,8 @@ def _dw_gemm(ext, dz: torch.Tensor, x2: torch.Tensor, out_dtype) -> torch.Tensor
         and dz.dtype == torch.bfloat16
         and ext.gemm_tn8p_supported(dz.shape[0], dz.shape[1], x2.shape[1])
     ):
-        return ext.gemm_tn_8p(dz, x2).to(out_dtype)
+        # bf16 weights: the split reduce rounds to bf16 itself (no cast pass)
+        return ext.gemm_tn_8p(dz, x2, 0, out_dtype == torch.bfloat16).to(out_dtype)
     return torch.matmul(dz.t(), x2)
 
 
@@ -110,7 +111,7 @@ def _dw_db_gemm(ext, dz: torch.Tensor, x2: torch.Tensor, out_dtype):
         and dz.dtype == torch.bfloat16
         and ext.gemm_tn8p_supported(dz.shape[0], dz.shape[1], x2.shape[1])
     ):
-        dw, db = ext.gemm_tn_8p_db(dz, x2)
+        dw, db = ext.gemm_tn_8p_db(dz, x2, 0, out_dtype == torch.bfloat16)
         return dw.to(out_dtype), db.to(dz.dtype)
     dw = torch.matmul(dz.t(), x2)
     if dz.is_cuda and dz.shape[-1] % 8 == 0:
