@@ -32,3 +32,9 @@ for B, H, L, causal, tag in [
     t_b = bench(lambda: ext.attn_bwd_fused(q, k, v, oc, do, lse, dq, dk, dv, causal, scale))
     print(f"{tag:18s} L={L:4d}: fwd {tf_fwd/t_f:6.1f} TF/s ({t_f*1e3:6.3f} ms)  "
           f"bwd {2.5*tf_fwd/t_b:6.1f} TF/s ({t_b*1e3:6.3f} ms)", flush=True)
+    if not causal and 81 <= L <= 256:
+        # resident domain: the two backward paths side by side
+        t_p = {p: bench(lambda p=p: ext.attn_bwd_fused(q, k, v, oc, do, lse, dq, dk, dv, causal, scale, p))
+               for p in ("tiled", "resident")}
+        print(f"{'':18s}         bwd tiled {2.5*tf_fwd/t_p['tiled']:6.1f} TF/s ({t_p['tiled']*1e3:6.3f} ms)  "
+              f"resident {2.5*tf_fwd/t_p['resident']:6.1f} TF/s ({t_p['resident']*1e3:6.3f} ms)", flush=True)

@@ -14,6 +14,11 @@
 //   attn_d2_kernel      — D[b,h,l] = rowsum(dO * O), stride-aware fp32
 //     (consumed by both kernels for dS = P*(dP - D)*scale).
 //
+// Two single-launch kernels take over where a whole (b, h) fits in LDS:
+//   attn_bwd_small_kernel    — Lq == Lk <= 80
+//   attn_bwd_resident_kernel — 81 <= Lq == Lk <= 256, non-causal (ViT-B L=197)
+// (both D = 64; see their header comments and the dispatch in attn_bwd_fused).
+//
 // All tensor arguments are (B,H,L,64) *views* with arbitrary (b,h,l) strides
 // and a contiguous innermost dim — q/k/v slices of the fused (B,L,3,H,64)
 // QKV projection and (B,L,H,64)-storage dO/O are consumed with zero permute
@@ -846,11 +851,309 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Resident fused backward (Lq == Lk = L, 81 <= L <= 256, D = 64, non-causal):
+// ONE kernel replaces the d2 + dkv + dq trio. One workgroup per (b, h) keeps
+// a whole operand pair in LDS block images and computes BOTH orientations
+// from them, so no P/dS tile is ever exchanged between waves and K, V, Q, dO
+// come from HBM once (the tiled pair reads each of them twice, from two
+// workgroups on different XCDs). ceil(L/32) waves, each owning the two
+// 16-row strips wave and wave + nwaves; two image slots (K/V, then Q/dO), so
+// LDS is 58 KiB at L = 197 and two workgroups share a CU: one loads or
+// stores while the other computes.
+//   phase 1 (strip = 16 queries): S^T = K.Q^T and dP^T = V.dO^T with
+//     A-fragments read ds_read_b128 from the K/V images and the strip's own
+//     Q/dO rows held in registers as B-fragments; keys are walked 32 at a
+//     time. delta[q] = rowsum(dO o O) of the strip's own 16 rows (one sweep
+//     over the keys; costs one read of O). dQ^T += K^T.dS^T with tr-read
+//     fragments of the K image.
+//   between the phases the wave takes its own K/V rows out of the images
+//     (phase-2 B-fragments) and Q/dO (L2-hot) replace K/V in the two slots.
+//   phase 2 (strip = 16 keys): S = Q.K^T and dP = dO.V^T, A-fragments from
+//     the Q/dO images; dV^T += dO^T.P and dK^T += Q^T.dS with tr-read
+//     fragments of the dO/Q images; lse[q] and delta[q] come from LDS.
+// The second GEMM of each phase takes its dS / P operand straight from the
+// accumulator registers of the first: lane (lo, hi) of two 16-row C tiles
+// t = 0, 1 holds rows 16t + 4hi + r (r = 0..3) of column lo, which is a
+// fragment X[lo][8hi + j] whose contraction slot 8hi + j stands for row
+// 4hi + j (j < 4) or 16 + 4hi + (j - 4) of the 32-row block. The images
+// therefore keep their 8 row-quads in NATURAL order (boff<> stores evens
+// first, which makes slot == row): ds_read_b64_tr_b16 at base + lane*8
+// fetches slot-quad sq from position (sq&1)*4 + (sq>>1), exactly the
+// row-quad the permuted fragment expects. The tr-read fragment is used as
+// the A operand and the P/dS fragment as B (the register contents of an A
+// and a B fragment of the same matrix are identical), so the accumulators
+// hold TRANSPOSED output tiles: lane = output row lo, 4 consecutive d, one
+// 8-byte store per tile instead of four 2-byte ones.
+// Within a 32-row x 16-d sub-block rows are 32 B apart, so the ds_read_b128
+// A-fragment reads (8 contiguous d of row lo) hit 16 distinct 16-B slots per
+// lane group.
+// Image rows >= L are zero; every global load is clamped to row L-1, every
+// store guarded by row < L; P and dS of padded rows are forced to exact 0.
+// Synchronisation: barrier 1 orders the K/V staging writes (images, lse,
+// zeroed delta) before every phase-1 read and before phase 1's delta
+// writes. Barrier 2 retires every read of the K/V images (phase 1 and the
+// phase-2 B-fragment loads) before Q/dO overwrite them, and orders phase
+// 1's delta writes before phase 2's delta reads. Barrier 3 publishes the
+// Q/dO images to phase 2. All three barriers and every tr read are outside
+// divergent control flow (the branches around them are wave-uniform), so
+// EXEC is all ones at each ds_read_b64_tr_b16.
+// ---------------------------------------------------------------------------
+
+constexpr int RES_LMIN = 81;
+constexpr int RES_LMAX = 256;
+
+__device__ __forceinline__ int noff(int row, int d) {
+  return (row >> 5) * 2048 + (d >> 4) * 512 + (row & 31) * 16 + (d & 15);
+}
+
+__global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
+    const bf16* __restrict__ o, const bf16* __restrict__ dO, const float* __restrict__ lse,
+    bf16* __restrict__ dq, bf16* __restrict__ dk, bf16* __restrict__ dv, int L, float scale,
+    int H, int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
+    int64_t v_sb, int64_t v_sh, int64_t v_sl, int64_t o_sb, int64_t o_sh, int64_t o_sl,
+    int64_t do_sb, int64_t do_sh, int64_t do_sl, int64_t dq_sb, int64_t dq_sh, int64_t dq_sl,
+    int64_t dk_sb, int64_t dk_sh, int64_t dk_sl, int64_t dv_sb, int64_t dv_sh,
+    int64_t dv_sl) {
+  constexpr int D = 64;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int LP = (L + 31) & ~31;  // image rows: whole 32-row blocks
+  const int IMG = LP * D;
+  short* imgA = reinterpret_cast<short*>(smem);  // K, then Q
+  short* imgB = imgA + IMG;                      // V, then dO
+  float* lse_s = reinterpret_cast<float*>(imgB + IMG);  // [LP]
+  float* dl_s = lse_s + LP;                             // [LP] delta
+
+  const int tid = threadIdx.x;
+  const int nthr = blockDim.x;  // 64 * LP/32: the image has exactly 4 16-B chunks per thread
+  const int nw = nthr / WAVE;
+  const int wave = tid / WAVE;
+  const int lane = tid % WAVE;
+  const int lo = lane & 15, hi = lane >> 4;
+  const int64_t bh = blockIdx.x;
+  const int64_t b = bh / H, h = bh % H;
+  const bf16* qp = q + b * q_sb + h * q_sh;
+  const bf16* kp = k + b * k_sb + h * k_sh;
+  const bf16* vp = v + b * v_sb + h * v_sh;
+  const bf16* op = o + b * o_sb + h * o_sh;
+  const bf16* dop = dO + b * do_sb + h * do_sh;
+  const int nblk = LP / 32;
+
+  // ---- a strip's own Q/dO rows (phase-1 B-fragments) and its delta ---------
+  bf16x8_t qb[2], dob[2];
+  float dl;
+  auto load_rows = [&](int s0) {
+    const int srow = min(s0 + lo, L - 1);
+    dl = 0.f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      qb[s] = *reinterpret_cast<const bf16x8_t*>(qp + (int64_t)srow * q_sl + 32 * s + hi * 8);
+      dob[s] = *reinterpret_cast<const bf16x8_t*>(dop + (int64_t)srow * do_sl + 32 * s + hi * 8);
+      const bf16x8_t ov =
+          *reinterpret_cast<const bf16x8_t*>(op + (int64_t)srow * o_sl + 32 * s + hi * 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dl += bfs2f(dob[s][j]) * bfs2f(ov[j]);
+    }
+    dl += __shfl_xor(dl, 16, WAVE);
+    dl += __shfl_xor(dl, 32, WAVE);  // delta[s0 + lo] = rowsum(dO o O)
+  };
+  load_rows(16 * wave);  // first strip
+
+  // ---- stage K, V + lse ----------------------------------------------------
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int idx = tid + it * nthr;
+    const int row = idx >> 3, d8 = (idx & 7) * 8;
+    const int rc = min(row, L - 1);
+    bf16x8_t kk = *reinterpret_cast<const bf16x8_t*>(kp + (int64_t)rc * k_sl + d8);
+    bf16x8_t vv = *reinterpret_cast<const bf16x8_t*>(vp + (int64_t)rc * v_sl + d8);
+    if (row >= L) kk = vv = bf16x8_t{};
+    const int off = noff(row, d8);
+    *reinterpret_cast<bf16x8_t*>(imgA + off) = kk;
+    *reinterpret_cast<bf16x8_t*>(imgB + off) = vv;
+  }
+  for (int i = tid; i < LP; i += nthr) {
+    lse_s[i] = i < L ? lse[bh * L + i] : 0.f;
+    dl_s[i] = 0.f;
+  }
+  __syncthreads();  // barrier 1
+
+  // ---- phase 1: wave = query strips wave, wave + nw -----------------------
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int s0 = 16 * (wave + i * nw);
+    if (s0 >= L) continue;  // wave-uniform
+    if (i == 1) load_rows(s0);
+    const bool sok = s0 + lo < L;
+    const float lse_q = lse_s[min(s0 + lo, L - 1)];
+    const float dli = dl;
+    if (hi == 0) dl_s[s0 + lo] = dli;
+    f32x4_t adq[4] = {};
+    for (int kb = 0; kb < nblk; ++kb) {
+      f32x4_t sc[2] = {}, dpc[2] = {};
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if (32 * kb + 16 * t >= L) continue;  // whole 16-key tile is padding (wave-uniform)
+        bf16x8_t ka[2], va[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const int off = noff(32 * kb + 16 * t + lo, 32 * s + hi * 8);
+          ka[s] = *reinterpret_cast<const bf16x8_t*>(imgA + off);
+          va[s] = *reinterpret_cast<const bf16x8_t*>(imgB + off);
+        }
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          sc[t] = MFMA16(ka[s], qb[s], sc[t]);
+          dpc[t] = MFMA16(va[s], dob[s], dpc[t]);
+        }
+        __builtin_amdgcn_s_setprio(0);
+      }
+      bf16x8_t dsa;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = 32 * kb + 16 * t + 4 * hi + r;
+          const bool ok = sok && key < L;
+          const float p = ok ? __expf(sc[t][r] * scale - lse_q) : 0.f;
+          const float ds = ok ? p * (dpc[t][r] - dli) * scale : 0.f;
+          dsa[4 * t + r] = f2bfs(ds);
+        }
+      }
+      bf16x8_t bfr[4];
+      tr_frag_x4((lds_cp)(const void*)(imgA + kb * 32 * D) + lane * 8, bfr);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) adq[dt] = MFMA16(bfr[dt], dsa, adq[dt]);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    // adq holds dQ^T tiles: lane = query lo, d = 16dt + 4hi + r -> 8-byte stores
+    if (sok) {
+      bf16* dqp = dq + b * dq_sb + h * dq_sh + (int64_t)(s0 + lo) * dq_sl + 4 * hi;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        bf16x4_tr pk;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pk[r] = f2bfs(adq[dt][r]);
+        *reinterpret_cast<bf16x4_tr*>(dqp + 16 * dt) = pk;
+      }
+    }
+  }
+
+  // ---- between the phases: Q/dO replace K/V in the two image slots --------
+  bf16x8_t qst[4], dst[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int idx = tid + it * nthr;
+    const int row = idx >> 3, d8 = (idx & 7) * 8;
+    const int rc = min(row, L - 1);
+    qst[it] = *reinterpret_cast<const bf16x8_t*>(qp + (int64_t)rc * q_sl + d8);
+    dst[it] = *reinterpret_cast<const bf16x8_t*>(dop + (int64_t)rc * do_sl + d8);
+    if (row >= L) qst[it] = dst[it] = bf16x8_t{};
+  }
+  // own K/V rows of the two key strips as phase-2 B-fragments, taken from
+  // the images before they are overwritten (image rows >= L are zero)
+  bf16x8_t kbf[2][2], vbf[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int srow = min(16 * (wave + i * nw) + lo, LP - 1);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int off = noff(srow, 32 * s + hi * 8);
+      kbf[i][s] = *reinterpret_cast<const bf16x8_t*>(imgA + off);
+      vbf[i][s] = *reinterpret_cast<const bf16x8_t*>(imgB + off);
+    }
+  }
+  __syncthreads();  // barrier 2: K/V images retired, every strip's delta in LDS
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int idx = tid + it * nthr;
+    const int off = noff(idx >> 3, (idx & 7) * 8);
+    *reinterpret_cast<bf16x8_t*>(imgA + off) = qst[it];
+    *reinterpret_cast<bf16x8_t*>(imgB + off) = dst[it];
+  }
+  __syncthreads();  // barrier 3: Q/dO images published
+
+  // ---- phase 2: wave = key strips wave, wave + nw --------------------------
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int s0 = 16 * (wave + i * nw);
+    if (s0 >= L) continue;  // wave-uniform
+    const bool sok = s0 + lo < L;
+    f32x4_t adk[4] = {}, adv[4] = {};
+    for (int qblk = 0; qblk < nblk; ++qblk) {
+      f32x4_t sc[2] = {}, dpc[2] = {};
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if (32 * qblk + 16 * t >= L) continue;  // whole 16-query tile is padding
+        bf16x8_t qa[2], da[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const int off = noff(32 * qblk + 16 * t + lo, 32 * s + hi * 8);
+          qa[s] = *reinterpret_cast<const bf16x8_t*>(imgA + off);
+          da[s] = *reinterpret_cast<const bf16x8_t*>(imgB + off);
+        }
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          sc[t] = MFMA16(qa[s], kbf[i][s], sc[t]);
+          dpc[t] = MFMA16(da[s], vbf[i][s], dpc[t]);
+        }
+        __builtin_amdgcn_s_setprio(0);
+      }
+      bf16x8_t pa, dsa;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int qi0 = 32 * qblk + 16 * t + 4 * hi;
+        const f32x4_t ls4 = *reinterpret_cast<const f32x4_t*>(lse_s + qi0);
+        const f32x4_t dl4 = *reinterpret_cast<const f32x4_t*>(dl_s + qi0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool ok = sok && qi0 + r < L;
+          const float p = ok ? __expf(sc[t][r] * scale - ls4[r]) : 0.f;
+          const float ds = ok ? p * (dpc[t][r] - dl4[r]) * scale : 0.f;
+          pa[4 * t + r] = f2bfs(p);
+          dsa[4 * t + r] = f2bfs(ds);
+        }
+      }
+      bf16x8_t bfr[4];  // one fragment set at a time (register budget)
+      tr_frag_x4((lds_cp)(const void*)(imgB + qblk * 32 * D) + lane * 8, bfr);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) adv[dt] = MFMA16(bfr[dt], pa, adv[dt]);
+      __builtin_amdgcn_s_setprio(0);
+      tr_frag_x4((lds_cp)(const void*)(imgA + qblk * 32 * D) + lane * 8, bfr);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) adk[dt] = MFMA16(bfr[dt], dsa, adk[dt]);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    // transposed tiles again: lane = key lo, d = 16dt + 4hi + r
+    if (sok) {
+      bf16* dkp = dk + b * dk_sb + h * dk_sh + (int64_t)(s0 + lo) * dk_sl + 4 * hi;
+      bf16* dvp = dv + b * dv_sb + h * dv_sh + (int64_t)(s0 + lo) * dv_sl + 4 * hi;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        bf16x4_tr pk, pv;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          pk[r] = f2bfs(adk[dt][r]);
+          pv[r] = f2bfs(adv[dt][r]);
+        }
+        *reinterpret_cast<bf16x4_tr*>(dkp + 16 * dt) = pk;
+        *reinterpret_cast<bf16x4_tr*>(dvp + 16 * dt) = pv;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o,
                     torch::Tensor dO, torch::Tensor lse, torch::Tensor dq, torch::Tensor dk,
-                    torch::Tensor dv, bool causal, double scale) {
+                    torch::Tensor dv, bool causal, double scale, std::string path) {
   // all tensors (B,H,L,64) views, innermost contiguous, arbitrary b/h/l strides
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(q.dim() == 4, "attn_bwd_fused: (B,H,L,D) expected");
@@ -864,8 +1167,58 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
   TORCH_CHECK(lse.is_contiguous() && lse.scalar_type() == torch::kFloat32);
   auto stream = at::hip::getCurrentHIPStream();
 
+  // path: "auto" picks small (L <= 80) / resident (81..RES_LMAX) / tiled;
+  // "tiled" forces d2 + dkv + dq; "resident" fails outside its domain
+  TORCH_CHECK(path == "auto" || path == "tiled" || path == "resident",
+              "attn_bwd_fused: path must be auto, tiled or resident, got ", path);
+  // the resident kernel stores 8 bytes at a time: rows must be 16-byte aligned
+  // (true of every view the model passes; anything else stays on the tiled path)
+  bool res_aligned = true;
+  for (auto* t : {&q, &k, &v, &o, &dO, &dq, &dk, &dv})
+    res_aligned = res_aligned && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0 &&
+                  t->stride(0) % 8 == 0 && t->stride(1) % 8 == 0 && t->stride(2) % 8 == 0;
+  const bool resident_ok = Dr == 64 && Lq == Lk && !causal && Lk >= RES_LMIN &&
+                           Lk <= RES_LMAX && res_aligned;
+  TORCH_CHECK(path != "resident" || resident_ok,
+              "attn_bwd_fused: path=resident needs D == 64, Lq == Lk, non-causal, ",
+              RES_LMIN, " <= L <= ", RES_LMAX, " and 16-byte aligned rows; got D=", Dr,
+              " Lq=", Lq, " Lk=", Lk, " causal=", causal, " aligned=", res_aligned);
+  if (path != "tiled" && resident_ok) {
+    // one wave per 32 rows (two 16-row strips each); two images + lse + delta
+    for (auto* t : {&q, &k, &v, &o, &dO, &dq, &dk, &dv})
+      TORCH_CHECK(t->size(0) == B && t->size(1) == H && t->size(2) == Lk && t->size(3) == 64,
+                  "attn_bwd_fused: resident path needs equal (B,H,L,64) shapes");
+    TORCH_CHECK(lse.numel() == (int64_t)B * H * Lk, "attn_bwd_fused: lse must be (B,H,L)");
+    const int LP = (Lk + 31) & ~31;
+    const size_t rshmem = (size_t)2 * LP * 64 * sizeof(short) + (size_t)2 * LP * sizeof(float);
+    auto kfn = attn_bwd_resident_kernel;
+    static bool attr_res = [&] {
+      const size_t mx =
+          (size_t)2 * RES_LMAX * 64 * sizeof(short) + (size_t)2 * RES_LMAX * sizeof(float);
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)mx));
+      return true;
+    }();
+    (void)attr_res;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)((int64_t)B * H)), dim3(LP / 32 * WAVE), rshmem, stream,
+                       reinterpret_cast<const bf16*>(q.data_ptr()),
+                       reinterpret_cast<const bf16*>(k.data_ptr()),
+                       reinterpret_cast<const bf16*>(v.data_ptr()),
+                       reinterpret_cast<const bf16*>(o.data_ptr()),
+                       reinterpret_cast<const bf16*>(dO.data_ptr()), lse.data_ptr<float>(),
+                       reinterpret_cast<bf16*>(dq.data_ptr()),
+                       reinterpret_cast<bf16*>(dk.data_ptr()),
+                       reinterpret_cast<bf16*>(dv.data_ptr()), Lk, (float)scale, H,
+                       q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
+                       k.stride(2), v.stride(0), v.stride(1), v.stride(2), o.stride(0),
+                       o.stride(1), o.stride(2), dO.stride(0), dO.stride(1), dO.stride(2),
+                       dq.stride(0), dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1),
+                       dk.stride(2), dv.stride(0), dv.stride(1), dv.stride(2));
+    return;
+  }
+
   // small-L fused path: one kernel, no delta buffer (Lq == Lk <= 80, D = 64)
-  if (Dr == 64 && Lq == Lk && Lk <= 80) {
+  if (path != "tiled" && Dr == 64 && Lq == Lk && Lk <= 80) {
     const dim3 sgrid((unsigned)((int64_t)B * H));
     const size_t sshmem = (3 * 96 * 64 + 3 * 80 * 88 + 8) * sizeof(short);
 #define SBWD_ARGS                                                                          \

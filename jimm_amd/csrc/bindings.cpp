@@ -41,7 +41,7 @@ torch::Tensor attn_d(torch::Tensor dO, torch::Tensor O);
 void attn_ds(torch::Tensor dp, torch::Tensor p, torch::Tensor D, double scale);
 void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o,
                     torch::Tensor dO, torch::Tensor lse, torch::Tensor dq, torch::Tensor dk,
-                    torch::Tensor dv, bool causal, double scale);
+                    torch::Tensor dv, bool causal, double scale, std::string path);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor B);
 bool gemm_supported(int64_t M, int64_t N, int64_t K, std::string dtype);
@@ -86,7 +86,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd_p", &attn_bwd_p, "attention bwd: S -> P in place (K15)");
   m.def("attn_d", &attn_d, "attention bwd: rowsum(dO*O) (K15)");
   m.def("attn_ds", &attn_ds, "attention bwd: dP -> dS in place (K15)");
-  m.def("attn_bwd_fused", &attn_bwd_fused, "fused flash attention backward (K15)");
+  m.def("attn_bwd_fused", &attn_bwd_fused,
+        "fused flash attention backward (K15); path: auto | tiled | resident",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dO"), py::arg("lse"),
+        py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal"), py::arg("scale"),
+        py::arg("path") = "auto");
   m.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 layout probe");
   m.def("mfma_probe32", &mfma_probe32, "MFMA 32x32x16 layout probe");
   m.def("gemm_supported", &gemm_supported, "MFMA GEMM shape support check");
