@@ -1,10 +1,10 @@
 """Within-probe interleaved A/B of the GEMM engines on the model-zoo shapes.
 
-Variants: 8p (gemm8p.hip, 8-phase counted-vmcnt), 2ph (gemm256.hip,
-vmcnt(0) 2-phase), blas (hipBLASLt via F.linear).  Interleaved rounds in one
-process (guide §5.4 rule 24); reports median and min ms per variant.
+Variants: 8p (gemm8p.hip, 8-phase counted-vmcnt), blas (hipBLASLt via
+F.linear).  Interleaved rounds in one process (guide §5.4 rule 24); reports
+the median ms per variant.
 
-Run: gpurun -- 'python benchmarks/gemm8p_ab.py'
+Run: python benchmarks/gemm8p_ab.py
 """
 
 import os, statistics, sys, time
@@ -64,18 +64,9 @@ def main():
         tf = 2 * M * N * K / 1e12
 
         sup8 = ext.gemm8p_supported(M, N, K)
-        sup2 = (M % 256 == 0) and (N % 256 == 0) and (K % 64 == 0)
 
-        os.environ["JIMM_AMD_GEMM_TILE"] = "0"
         f8 = lambda: ext.linear_fwd(x, w, b, act, None, False)
         fb = lambda: torch.nn.functional.linear(x, w, b)
-
-        def f2():
-            os.environ["JIMM_AMD_GEMM_TILE"] = "256"
-            try:
-                return ext.linear_fwd(x, w, b, act, None, False)
-            finally:
-                os.environ["JIMM_AMD_GEMM_TILE"] = "0"
 
         # correctness first (8p vs fp32 reference)
         if sup8:
@@ -85,18 +76,14 @@ def main():
         else:
             err = float("nan")
 
-        res = {"8p": [], "2ph": [], "blas": []}
+        res = {"8p": [], "blas": []}
         for _ in range(2):  # warmup all variants
             if sup8:
                 f8()
-            if sup2:
-                f2()
             fb()
         for _ in range(ROUNDS):
             if sup8:
                 res["8p"].append(time_once(f8))
-            if sup2:
-                res["2ph"].append(time_once(f2))
             res["blas"].append(time_once(fb))
 
         def fmt(ts):
@@ -107,7 +94,7 @@ def main():
 
         print(
             f"M={M:6d} N={N:5d} K={K:5d} {act or '-':9s} "
-            f"8p {fmt(res['8p'])}  2ph {fmt(res['2ph'])}  blas {fmt(res['blas'])}  "
+            f"8p {fmt(res['8p'])}  blas {fmt(res['blas'])}  "
             f"relerr {err:.2e}",
             flush=True,
         )

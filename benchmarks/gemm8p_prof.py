@@ -1,6 +1,6 @@
 """Run ONE GEMM engine repeatedly (for rocprofv3 PMC collection).
 
-env: SHAPE="M,N,K" (default 4096,4096,4096), ENGINE=8p|2ph|blas, ITERS.
+env: SHAPE="M,N,K" (default 4096,4096,4096), ENGINE=8p|blas, ITERS.
 """
 
 import os, sys, time
@@ -23,8 +23,6 @@ x = (torch.rand(M, K, device=dev) * 2 - 1).bfloat16()
 w = ((torch.rand(N, K, device=dev) * 2 - 1) / K**0.5).bfloat16()
 b = torch.randn(N, device=dev).bfloat16()
 
-if engine == "2ph":
-    os.environ["JIMM_AMD_GEMM_TILE"] = "256"
 fn = (lambda: torch.nn.functional.linear(x, w, b)) if engine == "blas" else (
     lambda: ext.linear_fwd(x, w, b, "", None, False))
 

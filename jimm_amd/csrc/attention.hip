@@ -25,14 +25,12 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
 
 constexpr int QBLK = 64;    // q rows per strip (16 per wave)
 // NSTRIP (q strips per workgroup) is a template param: 4 = fewer K/V
@@ -40,69 +38,13 @@ constexpr int QBLK = 64;    // q rows per strip (16 per wave)
 // (JIMM_AMD_ATTN_NSTRIP selects; default 4)
 constexpr int KVBLK = 64;   // keys per LDS tile
 
-// Head dims beyond 64: template on the PADDED head dim
-// DP in {64, 96, 128} (d-fragments need multiples of 32); the runtime D
-// (72, 80 pad to 96) guards ragged loads/stores — 8-element chunks are
-// all-in or all-out since every supported D is a multiple of 8.
-template <int DP>
-__device__ __forceinline__ bf16x8_t ld8g(const bf16* p, int off, int Dr) {
-  if (DP == 64 || off + 8 <= Dr) return *reinterpret_cast<const bf16x8_t*>(p + off);
-  return bf16x8_t{};
-}
-
-// V block image (the gemm_tn8p.hip recipe, see attention_bwd_fused.hip):
-// [64 key][DP d] stored as [key-half][d16][8 key-quads evens-first][4][16],
-// written with vector ds_write_b128 from the row-major staging registers
-// and read as PV B-fragments with batched ds_read_b64_tr_b16 at per-lane
-// address base + lane*8 B.
-template <int ND>
-__device__ __forceinline__ int boff_f(int q, int d) {
-  const int qp = (q >> 2) & 7;
-  const int qpos = (qp & 1) * 4 + (qp >> 1);
-  return (q >> 5) * (32 * ND) + (d >> 4) * 512 + qpos * 64 + (q & 3) * 16 + (d & 15);
-}
-
-typedef short bf16x4_trf __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(3))) char* lds_cpf;
-
-__device__ __forceinline__ void trf_x4(lds_cpf base, bf16x8_t (&out)[4]) {
-  bf16x4_trf a0l, a0h, a1l, a1h, a2l, a2h, a3l, a3h;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8 offset:0\n\t"
-      "ds_read_b64_tr_b16 %1, %8 offset:512\n\t"
-      "ds_read_b64_tr_b16 %2, %8 offset:1024\n\t"
-      "ds_read_b64_tr_b16 %3, %8 offset:1536\n\t"
-      "ds_read_b64_tr_b16 %4, %8 offset:2048\n\t"
-      "ds_read_b64_tr_b16 %5, %8 offset:2560\n\t"
-      "ds_read_b64_tr_b16 %6, %8 offset:3072\n\t"
-      "ds_read_b64_tr_b16 %7, %8 offset:3584\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(a0l), "=&v"(a0h), "=&v"(a1l), "=&v"(a1h), "=&v"(a2l), "=&v"(a2h),
-        "=&v"(a3l), "=&v"(a3h)
-      : "v"(base)
-      : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  out[0] = __builtin_shufflevector(a0l, a0h, 0, 1, 2, 3, 4, 5, 6, 7);
-  out[1] = __builtin_shufflevector(a1l, a1h, 0, 1, 2, 3, 4, 5, 6, 7);
-  out[2] = __builtin_shufflevector(a2l, a2h, 0, 1, 2, 3, 4, 5, 6, 7);
-  out[3] = __builtin_shufflevector(a3l, a3h, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-__device__ __forceinline__ void trf_x2(lds_cpf base, bf16x8_t (&out)[2]) {
-  bf16x4_trf a0l, a0h, a1l, a1h;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %4 offset:0\n\t"
-      "ds_read_b64_tr_b16 %1, %4 offset:512\n\t"
-      "ds_read_b64_tr_b16 %2, %4 offset:1024\n\t"
-      "ds_read_b64_tr_b16 %3, %4 offset:1536\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(a0l), "=&v"(a0h), "=&v"(a1l), "=&v"(a1h)
-      : "v"(base)
-      : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  out[0] = __builtin_shufflevector(a0l, a0h, 0, 1, 2, 3, 4, 5, 6, 7);
-  out[1] = __builtin_shufflevector(a1l, a1h, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+// Head dims beyond 64: the kernel is templated on the
+// padded head dim DP and loads through ld8g<DP> (mfma.h).
+//
+// V block image (boff<DP>, mfma.h): [64 key][DP d], written with vector
+// ds_write_b128 from the row-major staging registers and read as PV
+// B-fragments with tr_frag_x4 / tr_frag_x2 at per-lane address
+// base + lane*8 B.
 
 template <bool CAUSAL, int NSTRIP, int DP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
@@ -207,8 +149,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
       const bf16x8_t v1 = st_valid ? vreg[cg][1] : bf16x8_t{};
       *reinterpret_cast<bf16x8_t*>(k_lds + bo + st_row * LDS_PITCH + c0) = k0;
       *reinterpret_cast<bf16x8_t*>(k_lds + bo + st_row * LDS_PITCH + c0 + 8) = k1;
-      *reinterpret_cast<bf16x8_t*>(vt_lds + bo + boff_f<DP>(st_row, c0)) = v0;
-      *reinterpret_cast<bf16x8_t*>(vt_lds + bo + boff_f<DP>(st_row, c0 + 8)) = v1;
+      *reinterpret_cast<bf16x8_t*>(vt_lds + bo + boff<DP>(st_row, c0)) = v0;
+      *reinterpret_cast<bf16x8_t*>(vt_lds + bo + boff<DP>(st_row, c0 + 8)) = v1;
     }
   };
 
@@ -309,10 +251,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
       for (int s = 0; s < 2; ++s) {
         if (kv0 + 32 * s >= kv_hi) continue;  // P = 0 for the whole step
         bf16x8_t vb[NT];
-        const lds_cpf bbase = (lds_cpf)(const void*)(vt_lds + sbo + s * 32 * DP) + lane * 8;
-        trf_x4(bbase, *reinterpret_cast<bf16x8_t(*)[4]>(&vb[0]));
-        if constexpr (NT == 6) trf_x2(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[2]>(&vb[4]));
-        if constexpr (NT == 8) trf_x4(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[4]>(&vb[4]));
+        const lds_cp bbase = (lds_cp)(const void*)(vt_lds + sbo + s * 32 * DP) + lane * 8;
+        tr_frag_x4(bbase, *reinterpret_cast<bf16x8_t(*)[4]>(&vb[0]));
+        if constexpr (NT == 6) tr_frag_x2(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[2]>(&vb[4]));
+        if constexpr (NT == 8) tr_frag_x4(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[4]>(&vb[4]));
         const bf16x8_t pa =
             *reinterpret_cast<const bf16x8_t*>(my_p + lo * LDS_PITCH + 32 * s + hi * 8);
         __builtin_amdgcn_s_setprio(1);
@@ -421,7 +363,7 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
       const int d8 = (idx & 7) * 8;
       bf16x8_t vv_{};
       if (key < Lk) vv_ = *reinterpret_cast<const bf16x8_t*>(vp + (int64_t)key * v_sl + d8);
-      *reinterpret_cast<bf16x8_t*>(vb + boff_f<D>(key, d8)) = vv_;
+      *reinterpret_cast<bf16x8_t*>(vb + boff<D>(key, d8)) = vv_;
     }
   }
   const int nq = (Lq + 15) / 16;
@@ -503,8 +445,8 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
     for (int s = 0; s < 3; ++s) {
       if (32 * s >= kv_hi) continue;
       bf16x8_t vbf[4];
-      const lds_cpf bbase = (lds_cpf)(const void*)(vb + s * 32 * D) + lane * 8;
-      trf_x4(bbase, vbf);
+      const lds_cp bbase = (lds_cp)(const void*)(vb + s * 32 * D) + lane * 8;
+      tr_frag_x4(bbase, vbf);
       const bf16x8_t pa = *reinterpret_cast<const bf16x8_t*>(pt + lo * PPITCH + 32 * s + hi * 8);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -600,13 +542,13 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
 #define ATTN_LAUNCH(C)                                                                     \
   do {                                                                                     \
     if (DP == 128)                                                                         \
-      hipLaunchKernelGGL((attn_fwd_kernel<C, 2, 128>), grid, dim3(256), shmem, stream, ATTN_ARGS); \
+      launch_lds<attn_fwd_kernel<C, 2, 128>>(grid, dim3(256), shmem, shmem, stream, ATTN_ARGS); \
     else if (DP == 96)                                                                     \
-      hipLaunchKernelGGL((attn_fwd_kernel<C, 2, 96>), grid, dim3(256), shmem, stream, ATTN_ARGS);  \
+      launch_lds<attn_fwd_kernel<C, 2, 96>>(grid, dim3(256), shmem, shmem, stream, ATTN_ARGS);  \
     else if (nstrip == 2)                                                                  \
-      hipLaunchKernelGGL((attn_fwd_kernel<C, 2, 64>), grid, dim3(256), shmem, stream, ATTN_ARGS);  \
+      launch_lds<attn_fwd_kernel<C, 2, 64>>(grid, dim3(256), shmem, shmem, stream, ATTN_ARGS);  \
     else                                                                                   \
-      hipLaunchKernelGGL((attn_fwd_kernel<C, 4, 64>), grid, dim3(256), shmem, stream, ATTN_ARGS);  \
+      launch_lds<attn_fwd_kernel<C, 4, 64>>(grid, dim3(256), shmem, shmem, stream, ATTN_ARGS);  \
   } while (0)
   if (causal) ATTN_LAUNCH(true); else ATTN_LAUNCH(false);
 #undef ATTN_LAUNCH

@@ -33,85 +33,22 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
-
 constexpr int BLK = 64;            // q rows / keys per workgroup tile
 
-// Head dims beyond 64: padded-D template DP in {64,96,128}; runtime Dr
-// guards ragged chunks (all supported D are multiples of 8, so 8-element
-// chunks are all-in or all-out). DP=64 keeps the round-1 fast path
+// Head dims beyond 64: padded-D template DP in {64,96,128}, ragged chunks
+// guarded by ld8g<DP> (mfma.h). DP=64 keeps the round-1 fast path
 // (NKV=2 / NQS=2 with cached fragments); DP>64 uses 1 tile per workgroup
 // with inline fragment reads to stay inside the register budget.
-template <int DP>
-__device__ __forceinline__ bf16x8_t ld8gb(const bf16* p, int off, int Dr) {
-  if (DP == 64 || off + 8 <= Dr) return *reinterpret_cast<const bf16x8_t*>(p + off);
-  return bf16x8_t{};
-}
-
-// Block-format image for transposed fragment reads (the gemm_tn8p.hip
-// recipe): a [64 q][ND d] tile stored as [q-half (q>>5)][d16 (d>>4)]
-// [8 q-quads, evens first][4][16] — written from row-major registers with
-// ds_write_b128 (two vector writes per 16-d chunk instead of 16 scalar
-// transpose stores, which were 8-way bank-conflicted), and read as MFMA
-// B-fragments with batched ds_read_b64_tr_b16 at per-lane address
-// base + lane*8 B (mapping verified by ext.tr16_probe).
-template <int ND>
-__device__ __forceinline__ int boff(int q, int d) {
-  const int qp = (q >> 2) & 7;
-  const int qpos = (qp & 1) * 4 + (qp >> 1);
-  return (q >> 5) * (32 * ND) + (d >> 4) * 512 + qpos * 64 + (q & 3) * 16 + (d & 15);
-}
-
-typedef short bf16x4_tr __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(3))) char* lds_cp;
-
-// 4 B-fragments (dt, dt+1, dt+2, dt+3) of one 32-contraction step from a
-// block image: 8 tr reads + lgkmcnt(0) in one asm (guide §5.7 form i).
-__device__ __forceinline__ void tr_frag_x4(lds_cp base, bf16x8_t (&out)[4]) {
-  bf16x4_tr a0l, a0h, a1l, a1h, a2l, a2h, a3l, a3h;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8 offset:0\n\t"
-      "ds_read_b64_tr_b16 %1, %8 offset:512\n\t"
-      "ds_read_b64_tr_b16 %2, %8 offset:1024\n\t"
-      "ds_read_b64_tr_b16 %3, %8 offset:1536\n\t"
-      "ds_read_b64_tr_b16 %4, %8 offset:2048\n\t"
-      "ds_read_b64_tr_b16 %5, %8 offset:2560\n\t"
-      "ds_read_b64_tr_b16 %6, %8 offset:3072\n\t"
-      "ds_read_b64_tr_b16 %7, %8 offset:3584\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(a0l), "=&v"(a0h), "=&v"(a1l), "=&v"(a1h), "=&v"(a2l), "=&v"(a2h),
-        "=&v"(a3l), "=&v"(a3h)
-      : "v"(base)
-      : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  out[0] = __builtin_shufflevector(a0l, a0h, 0, 1, 2, 3, 4, 5, 6, 7);
-  out[1] = __builtin_shufflevector(a1l, a1h, 0, 1, 2, 3, 4, 5, 6, 7);
-  out[2] = __builtin_shufflevector(a2l, a2h, 0, 1, 2, 3, 4, 5, 6, 7);
-  out[3] = __builtin_shufflevector(a3l, a3h, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-__device__ __forceinline__ void tr_frag_x2(lds_cp base, bf16x8_t (&out)[2]) {
-  bf16x4_tr a0l, a0h, a1l, a1h;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %4 offset:0\n\t"
-      "ds_read_b64_tr_b16 %1, %4 offset:512\n\t"
-      "ds_read_b64_tr_b16 %2, %4 offset:1024\n\t"
-      "ds_read_b64_tr_b16 %3, %4 offset:1536\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(a0l), "=&v"(a0h), "=&v"(a1l), "=&v"(a1h)
-      : "v"(base)
-      : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  out[0] = __builtin_shufflevector(a0l, a0h, 0, 1, 2, 3, 4, 5, 6, 7);
-  out[1] = __builtin_shufflevector(a1l, a1h, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+//
+// Transposed operands come from block-format images: boff<ND> places an
+// element, tr_frag_x4 / tr_frag_x2 read the fragments back (mfma.h).
 
 // ---------------------------------------------------------------------------
 // D = rowsum(dO * O), stride-aware
@@ -217,8 +154,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
     const int key = min(min(ti, ntk - 1) * BLK + 16 * wave + lo, Lk - 1);
 #pragma unroll
     for (int t = 0; t < NS; ++t) {
-      ka[s][t] = ld8gb<DP>(kp + (int64_t)key * k_sl, 32 * t + hi * 8, Dr);
-      va[s][t] = ld8gb<DP>(vp + (int64_t)key * v_sl, 32 * t + hi * 8, Dr);
+      ka[s][t] = ld8g<DP>(kp + (int64_t)key * k_sl, 32 * t + hi * 8, Dr);
+      va[s][t] = ld8g<DP>(vp + (int64_t)key * v_sl, 32 * t + hi * 8, Dr);
     }
   }
 
@@ -245,8 +182,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
       if (cg * 64 + st_c0 >= DP) continue;
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
-        qreg[cg][hh] = ld8gb<DP>(qp + (int64_t)qr * q_sl, cg * 64 + st_c0 + hh * 8, Dr);
-        doreg[cg][hh] = ld8gb<DP>(dop + (int64_t)qr * do_sl, cg * 64 + st_c0 + hh * 8, Dr);
+        qreg[cg][hh] = ld8g<DP>(qp + (int64_t)qr * q_sl, cg * 64 + st_c0 + hh * 8, Dr);
+        doreg[cg][hh] = ld8g<DP>(dop + (int64_t)qr * do_sl, cg * 64 + st_c0 + hh * 8, Dr);
       }
     }
   };
@@ -479,8 +416,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
     const int qrow = min(q0 + lo, Lq - 1);
 #pragma unroll
     for (int t = 0; t < NS; ++t) {
-      qa[s][t] = ld8gb<DP>(qp + (int64_t)qrow * q_sl, 32 * t + hi * 8, Dr);
-      doa[s][t] = ld8gb<DP>(dop + (int64_t)qrow * do_sl, 32 * t + hi * 8, Dr);
+      qa[s][t] = ld8g<DP>(qp + (int64_t)qrow * q_sl, 32 * t + hi * 8, Dr);
+      doa[s][t] = ld8g<DP>(dop + (int64_t)qrow * do_sl, 32 * t + hi * 8, Dr);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -511,8 +448,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
       if (cg * 64 + st_c0 >= DP) continue;
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
-        kreg[cg][hh] = ld8gb<DP>(kp + (int64_t)kr * k_sl, cg * 64 + st_c0 + hh * 8, Dr);
-        vreg[cg][hh] = ld8gb<DP>(vp + (int64_t)kr * v_sl, cg * 64 + st_c0 + hh * 8, Dr);
+        kreg[cg][hh] = ld8g<DP>(kp + (int64_t)kr * k_sl, cg * 64 + st_c0 + hh * 8, Dr);
+        vreg[cg][hh] = ld8g<DP>(vp + (int64_t)kr * v_sl, cg * 64 + st_c0 + hh * 8, Dr);
       }
     }
   };
@@ -778,7 +715,7 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
     dsum += __shfl_xor(dsum, 32, WAVE);  // delta[q] == rowsum(dO o O)
 #pragma unroll
     for (int kt = 0; kt < 5; ++kt) {
-      bf16x4_tr ds4;
+      bf16x4 ds4;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = 16 * kt + 4 * hi + r;
@@ -788,7 +725,7 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
         DST[key * TP + q_idx] = f2bfs(ds);
         ds4[r] = f2bfs(ds);
       }
-      *reinterpret_cast<bf16x4_tr*>(DSQ + q_idx * TP + 16 * kt + 4 * hi) = ds4;
+      *reinterpret_cast<bf16x4*>(DSQ + q_idx * TP + 16 * kt + 4 * hi) = ds4;
     }
     // dQ strip = dS @ K (B = tr fragments of the K image)
     f32x4_t adq[4] = {};
@@ -1034,10 +971,10 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
       bf16* dqp = dq + b * dq_sb + h * dq_sh + (int64_t)(s0 + lo) * dq_sl + 4 * hi;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        bf16x4_tr pk;
+        bf16x4 pk;
 #pragma unroll
         for (int r = 0; r < 4; ++r) pk[r] = f2bfs(adq[dt][r]);
-        *reinterpret_cast<bf16x4_tr*>(dqp + 16 * dt) = pk;
+        *reinterpret_cast<bf16x4*>(dqp + 16 * dt) = pk;
       }
     }
   }
@@ -1136,14 +1073,14 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
       bf16* dvp = dv + b * dv_sb + h * dv_sh + (int64_t)(s0 + lo) * dv_sl + 4 * hi;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        bf16x4_tr pk, pv;
+        bf16x4 pk, pv;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           pk[r] = f2bfs(adk[dt][r]);
           pv[r] = f2bfs(adv[dt][r]);
         }
-        *reinterpret_cast<bf16x4_tr*>(dkp + 16 * dt) = pk;
-        *reinterpret_cast<bf16x4_tr*>(dvp + 16 * dt) = pv;
+        *reinterpret_cast<bf16x4*>(dkp + 16 * dt) = pk;
+        *reinterpret_cast<bf16x4*>(dvp + 16 * dt) = pv;
       }
     }
   }
@@ -1191,16 +1128,12 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
     TORCH_CHECK(lse.numel() == (int64_t)B * H * Lk, "attn_bwd_fused: lse must be (B,H,L)");
     const int LP = (Lk + 31) & ~31;
     const size_t rshmem = (size_t)2 * LP * 64 * sizeof(short) + (size_t)2 * LP * sizeof(float);
-    auto kfn = attn_bwd_resident_kernel;
-    static bool attr_res = [&] {
-      const size_t mx =
-          (size_t)2 * RES_LMAX * 64 * sizeof(short) + (size_t)2 * RES_LMAX * sizeof(float);
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)mx));
-      return true;
-    }();
-    (void)attr_res;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)((int64_t)B * H)), dim3(LP / 32 * WAVE), rshmem, stream,
+    // the LDS limit is raised once, to the largest supported L
+    constexpr size_t rshmem_max =
+        (size_t)2 * RES_LMAX * 64 * sizeof(short) + (size_t)2 * RES_LMAX * sizeof(float);
+    launch_lds<attn_bwd_resident_kernel>(
+                       dim3((unsigned)((int64_t)B * H)), dim3(LP / 32 * WAVE), rshmem, rshmem_max,
+                       stream,
                        reinterpret_cast<const bf16*>(q.data_ptr()),
                        reinterpret_cast<const bf16*>(k.data_ptr()),
                        reinterpret_cast<const bf16*>(v.data_ptr()),
@@ -1234,25 +1167,10 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
                      dO.stride(1), dO.stride(2), dq.stride(0), dq.stride(1), dq.stride(2), \
                      dk.stride(0), dk.stride(1), dk.stride(2), dv.stride(0), dv.stride(1), \
                      dv.stride(2)
-    if (causal) {
-      auto kfn = attn_bwd_small_kernel<true>;
-      static bool attr_sb_c = [&] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sshmem);
-        return true;
-      }();
-      (void)attr_sb_c;
-      hipLaunchKernelGGL(kfn, sgrid, dim3(320), sshmem, stream, SBWD_ARGS);
-    } else {
-      auto kfn = attn_bwd_small_kernel<false>;
-      static bool attr_sb_n = [&] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sshmem);
-        return true;
-      }();
-      (void)attr_sb_n;
-      hipLaunchKernelGGL(kfn, sgrid, dim3(320), sshmem, stream, SBWD_ARGS);
-    }
+    if (causal)
+      launch_lds<attn_bwd_small_kernel<true>>(sgrid, dim3(320), sshmem, sshmem, stream, SBWD_ARGS);
+    else
+      launch_lds<attn_bwd_small_kernel<false>>(sgrid, dim3(320), sshmem, sshmem, stream, SBWD_ARGS);
 #undef SBWD_ARGS
     return;
   }
@@ -1299,17 +1217,17 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
 #define DKV_LAUNCH(C)                                                                        \
   do {                                                                                       \
     if (DP == 128)                                                                           \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<C, 1, 128>), grid_dkv, dim3(256), shmem_dkv,   \
-                         stream, DKV_ARGS);                                                  \
+      launch_lds<attn_bwd_dkv_kernel<C, 1, 128>>(grid_dkv, dim3(256), shmem_dkv, shmem_dkv,  \
+                                                 stream, DKV_ARGS);                          \
     else if (DP == 96)                                                                       \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<C, 1, 96>), grid_dkv, dim3(256), shmem_dkv,    \
-                         stream, DKV_ARGS);                                                  \
+      launch_lds<attn_bwd_dkv_kernel<C, 1, 96>>(grid_dkv, dim3(256), shmem_dkv, shmem_dkv,   \
+                                                stream, DKV_ARGS);                           \
     else if (nkv == 1)                                                                       \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<C, 1, 64>), grid_dkv, dim3(256), shmem_dkv,    \
-                         stream, DKV_ARGS);                                                  \
+      launch_lds<attn_bwd_dkv_kernel<C, 1, 64>>(grid_dkv, dim3(256), shmem_dkv, shmem_dkv,   \
+                                                stream, DKV_ARGS);                           \
     else                                                                                     \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<C, 2, 64>), grid_dkv, dim3(256), shmem_dkv,    \
-                         stream, DKV_ARGS);                                                  \
+      launch_lds<attn_bwd_dkv_kernel<C, 2, 64>>(grid_dkv, dim3(256), shmem_dkv, shmem_dkv,   \
+                                                stream, DKV_ARGS);                           \
   } while (0)
 #define DQ_ARGS                                                                              \
                      reinterpret_cast<const bf16*>(q.data_ptr()),                            \
@@ -1324,14 +1242,14 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
 #define DQ_LAUNCH(C)                                                                         \
   do {                                                                                       \
     if (DP == 128)                                                                           \
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<C, 1, 128>), grid_dq, dim3(256), shmem_dq,      \
-                         stream, DQ_ARGS);                                                   \
+      launch_lds<attn_bwd_dq_kernel<C, 1, 128>>(grid_dq, dim3(256), shmem_dq, shmem_dq,      \
+                                                stream, DQ_ARGS);                            \
     else if (DP == 96)                                                                       \
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<C, 1, 96>), grid_dq, dim3(256), shmem_dq,       \
-                         stream, DQ_ARGS);                                                   \
+      launch_lds<attn_bwd_dq_kernel<C, 1, 96>>(grid_dq, dim3(256), shmem_dq, shmem_dq,       \
+                                               stream, DQ_ARGS);                             \
     else                                                                                     \
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<C, 2, 64>), grid_dq, dim3(256), shmem_dq,       \
-                         stream, DQ_ARGS);                                                   \
+      launch_lds<attn_bwd_dq_kernel<C, 2, 64>>(grid_dq, dim3(256), shmem_dq, shmem_dq,       \
+                                               stream, DQ_ARGS);                             \
   } while (0)
   if (causal) {
     DKV_LAUNCH(true);

@@ -231,14 +231,6 @@ __global__ void embed_pos_kernel(const int64_t* __restrict__ ids, const T* __res
   }
 }
 
-int act_code(const std::string& act) {
-  if (act.empty()) return ACT_NONE;
-  if (act == "gelu") return ACT_GELU;
-  if (act == "gelu_tanh") return ACT_GELU_TANH;
-  if (act == "quickgelu") return ACT_QUICKGELU;
-  TORCH_CHECK(false, "unknown activation ", act);
-}
-
 template <typename T>
 void launch_bias_act(torch::Tensor& z, const c10::optional<torch::Tensor>& bias,
                      const c10::optional<torch::Tensor>& res, torch::Tensor& y, int M,
@@ -273,6 +265,15 @@ void launch_bias_act(torch::Tensor& z, const c10::optional<torch::Tensor>& bias,
 }
 
 }  // namespace
+
+// the one activation-name parse; the GEMM front ends share it (mfma.h)
+int act_code(const std::string& act) {
+  if (act.empty()) return ACT_NONE;
+  if (act == "gelu") return ACT_GELU;
+  if (act == "gelu_tanh") return ACT_GELU_TANH;
+  if (act == "quickgelu") return ACT_QUICKGELU;
+  TORCH_CHECK(false, "unknown activation ", act);
+}
 
 torch::Tensor bias_act_fwd(torch::Tensor z, c10::optional<torch::Tensor> bias,
                            std::string act, c10::optional<torch::Tensor> residual) {

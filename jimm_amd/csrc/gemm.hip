@@ -19,18 +19,20 @@
 //   * XCD-aware bijective blockIdx remap (guide T1) for L2 tile locality.
 //
 // Ragged shapes fall back to the generic guarded kernel below.
+//
+// linear_fwd sends every shape the 8-phase 256x256-tile kernel supports
+// (gemm8p.hip: N%256==0, K>=128, any M) there; the two kernels in this file
+// take the rest: N%256!=0 (SigLIP-so400m's 1152), ragged N, or K==64.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int PITCH = BK + 8;  // generic path only
@@ -55,14 +57,8 @@ __device__ __forceinline__ void stage_tile_glds(const bf16* __restrict__ gsrc, i
     const int row = off >> 7;              // /128
     const int chunk = (off >> 4) & 7;      // 16B chunk within row
     const int src_chunk = chunk ^ (row & 7);
-    const bf16* g = gsrc + (int64_t)row * ldg + src_chunk * 8;
-    // C-style casts perform the addrspace conversion (generic->AS1/AS3);
-    // reinterpret_cast refuses (same idiom as CK's c_style_pointer_cast)
-    typedef const __attribute__((address_space(1))) unsigned int* gp_t;
-    typedef __attribute__((address_space(3))) unsigned int* lp_t;
-    __builtin_amdgcn_global_load_lds((gp_t)(const void*)g,
-                                     (lp_t)(void*)(reinterpret_cast<char*>(lds_base) + round * 4096 + wave * 1024),
-                                     16, 0, 0);
+    glds16(gsrc + (int64_t)row * ldg + src_chunk * 8,
+           reinterpret_cast<char*>(lds_base) + round * 4096 + wave * 1024);
   }
 }
 
@@ -89,13 +85,7 @@ __global__ __launch_bounds__(256) void gemm_nt_fast_kernel(
 
   // XCD-aware bijective remap of the linear tile id (guide T1)
   const int mt = M / BM, nt = N / BN;
-  const int nwg = mt * nt;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, mt * nt);
   const int m0 = (wg / nt) * BM;
   const int n0 = (wg % nt) * BN;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
@@ -137,12 +127,7 @@ __global__ __launch_bounds__(256) void gemm_nt_fast_kernel(
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const int n = n0 + wn + 16 * ni + lo;
-        float vpre = acc[mi][ni][r];
-        if (HAS_BIAS) vpre += bias[n];
-        if (SAVE_PRE) Z[(int64_t)m * N + n] = f2bf(vpre);
-        float vy = act_fwd(vpre, ACT);
-        if (HAS_RES) vy += bf2f(res[(int64_t)m * N + n]);
-        Y[(int64_t)m * N + n] = f2bf(vy);
+        gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE_PRE>(acc[mi][ni][r], m, n, N, bias, res, Y, Z);
       }
     }
   }
@@ -237,12 +222,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(
       for (int ni = 0; ni < 4; ++ni) {
         const int n = n0 + wn + 16 * ni + lo;
         if (n >= N) continue;
-        float vpre = acc[mi][ni][r];
-        if (HAS_BIAS) vpre += bias[n];
-        if (SAVE_PRE) Z[(int64_t)m * N + n] = f2bf(vpre);
-        float vy = act_fwd(vpre, ACT);
-        if (HAS_RES) vy += bf2f(res[(int64_t)m * N + n]);
-        Y[(int64_t)m * N + n] = f2bf(vy);
+        gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE_PRE>(acc[mi][ni][r], m, n, N, bias, res, Y, Z);
       }
     }
   }
@@ -250,25 +230,11 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(
 
 }  // namespace
 
-// 256x256-tile kernels: 8-phase (gemm8p.hip, the default — deep-pipelined
-// counted-vmcnt schedule) and the older 2-phase (gemm256.hip, kept for A/B
-// via JIMM_AMD_GEMM_TILE=256).
-bool gemm256_supported(int64_t M, int64_t N, int64_t K);
-void gemm_nt_256(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias_f32,
-                 std::string act, c10::optional<torch::Tensor> residual, torch::Tensor y,
-                 c10::optional<torch::Tensor> z);
+// 8-phase 256x256-tile kernel (gemm8p.hip)
 bool gemm8p_supported(int64_t M, int64_t N, int64_t K);
 void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias_f32,
                 std::string act, c10::optional<torch::Tensor> residual, torch::Tensor y,
                 c10::optional<torch::Tensor> z);
-
-static int gemm_tile_mode() {
-  // 0 = auto (8-phase when supported), 256 = force 2-phase 256, 128 = force
-  // the 128-tile kernel (debug/A-B only)
-  const char* env = getenv("JIMM_AMD_GEMM_TILE");
-  if (!env) return 0;
-  return atoi(env);
-}
 
 bool gemm_supported(int64_t M, int64_t N, int64_t K, std::string dtype) {
   if (dtype != "torch.bfloat16") return false;
@@ -286,73 +252,45 @@ std::vector<torch::Tensor> linear_fwd(torch::Tensor x, torch::Tensor w,
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K && K % BK == 0);
   auto y = torch::empty({M, N}, x.options());
-  torch::Tensor z;
+  torch::Tensor z;  // stays undefined (None in Python) unless save_z
   if (save_z) z = torch::empty({M, N}, x.options());
   c10::optional<torch::Tensor> bf;
   if (bias) bf = bias->contiguous().to(torch::kFloat32);
-  int act_code = ACT_NONE;
-  if (act == "gelu") act_code = ACT_GELU;
-  else if (act == "gelu_tanh") act_code = ACT_GELU_TANH;
-  else if (act == "quickgelu") act_code = ACT_QUICKGELU;
-  else TORCH_CHECK(act.empty(), "unknown act ", act);
 
-  const int tile_mode = gemm_tile_mode();
-  if (tile_mode == 0 && gemm8p_supported(M, N, K)) {
+  if (gemm8p_supported(M, N, K)) {
     c10::optional<torch::Tensor> zopt;
     if (save_z) zopt = z;
     gemm_nt_8p(x, w, bf, act, residual, y, zopt);
-    if (save_z) return {y, z};
-    return {y, torch::Tensor()};
-  }
-  if (tile_mode != 128 && gemm256_supported(M, N, K)) {
-    c10::optional<torch::Tensor> zopt;
-    if (save_z) zopt = z;
-    gemm_nt_256(x, w, bf, act, residual, y, zopt);
-    if (save_z) return {y, z};
-    return {y, torch::Tensor()};
+    return {y, z};
   }
 
   auto stream = at::hip::getCurrentHIPStream();
-  const bf16* resp = residual ? reinterpret_cast<const bf16*>(residual->data_ptr()) : nullptr;
+  const bf16* xp = reinterpret_cast<const bf16*>(x.data_ptr());
+  const bf16* wp = reinterpret_cast<const bf16*>(w.data_ptr());
   const float* biasp = bf ? bf->data_ptr<float>() : nullptr;
+  const bf16* resp = residual ? reinterpret_cast<const bf16*>(residual->data_ptr()) : nullptr;
+  bf16* yp = reinterpret_cast<bf16*>(y.data_ptr());
   bf16* zp = save_z ? reinterpret_cast<bf16*>(z.data_ptr()) : nullptr;
   const bool fast = (M % BM == 0) && (N % BN == 0);
-
-#define LAUNCH(ACTC, HB, HR, SP)                                                          \
-  do {                                                                                    \
-    if (fast) {                                                                           \
-      hipLaunchKernelGGL((gemm_nt_fast_kernel<ACTC, HB, HR, SP>),                         \
-                         dim3((M / BM) * (N / BN)), dim3(256), 4 * 8192 * sizeof(short),  \
-                         stream, reinterpret_cast<const bf16*>(x.data_ptr()),             \
-                         reinterpret_cast<const bf16*>(w.data_ptr()), biasp, resp,        \
-                         reinterpret_cast<bf16*>(y.data_ptr()), zp, M, N, K);             \
-    } else {                                                                              \
-      hipLaunchKernelGGL((gemm_nt_kernel<ACTC, HB, HR, SP>),                              \
-                         dim3((M + BM - 1) / BM, (N + BN - 1) / BN), dim3(256),           \
-                         2 * (BM + BN) * PITCH * sizeof(short), stream,                   \
-                         reinterpret_cast<const bf16*>(x.data_ptr()),                     \
-                         reinterpret_cast<const bf16*>(w.data_ptr()), biasp, resp,        \
-                         reinterpret_cast<bf16*>(y.data_ptr()), zp, M, N, K);             \
-    }                                                                                     \
-  } while (0)
-#define DISPATCH_ACT(HB, HR, SP)                                                          \
-  switch (act_code) {                                                                     \
-    case ACT_NONE: LAUNCH(ACT_NONE, HB, HR, SP); break;                                   \
-    case ACT_GELU: LAUNCH(ACT_GELU, HB, HR, SP); break;                                   \
-    case ACT_GELU_TANH: LAUNCH(ACT_GELU_TANH, HB, HR, SP); break;                         \
-    case ACT_QUICKGELU: LAUNCH(ACT_QUICKGELU, HB, HR, SP); break;                         \
-  }
-  const bool hb = bias.has_value(), hr = residual.has_value();
-  if (hb && hr && save_z) DISPATCH_ACT(true, true, true)
-  else if (hb && hr) DISPATCH_ACT(true, true, false)
-  else if (hb && save_z) DISPATCH_ACT(true, false, true)
-  else if (hb) DISPATCH_ACT(true, false, false)
-  else if (hr && save_z) DISPATCH_ACT(false, true, true)
-  else if (hr) DISPATCH_ACT(false, true, false)
-  else if (save_z) DISPATCH_ACT(false, false, true)
-  else DISPATCH_ACT(false, false, false)
-#undef DISPATCH_ACT
-#undef LAUNCH
-  if (save_z) return {y, z};
-  return {y, torch::Tensor()};
+  with_act(act_code(act), [&](auto act_c) {
+    with_flags(
+        [&](auto hb, auto hr, auto sp, auto fast_c) {
+          constexpr int A = decltype(act_c)::value;
+          constexpr bool HB = decltype(hb)::value, HR = decltype(hr)::value,
+                         SP = decltype(sp)::value;
+          if constexpr (decltype(fast_c)::value) {
+            constexpr size_t shmem = 4 * 8192 * sizeof(short);
+            launch_lds<gemm_nt_fast_kernel<A, HB, HR, SP>>(dim3((M / BM) * (N / BN)), dim3(256),
+                                                           shmem, shmem, stream, xp, wp, biasp,
+                                                           resp, yp, zp, M, N, K);
+          } else {
+            constexpr size_t shmem = 2 * (BM + BN) * PITCH * sizeof(short);
+            launch_lds<gemm_nt_kernel<A, HB, HR, SP>>(
+                dim3((M + BM - 1) / BM, (N + BN - 1) / BN), dim3(256), shmem, shmem, stream, xp,
+                wp, biasp, resp, yp, zp, M, N, K);
+          }
+        },
+        bias.has_value(), residual.has_value(), save_z, fast);
+  });
+  return {y, z};
 }

@@ -48,22 +48,16 @@
 #include <hip/hip_fp8.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
-
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int NTHREADS = 512;
 constexpr int HALF_BYTES = 128 * BK * 2;  // 16 KiB per half-image
-
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("s_barrier" ::: "memory");
-}
 
 // Per-lane glds source base for one half-image (row/chunk fixed per lane;
 // only the K offset advances — the K-loop adds kt*128 B).  A half-image is
@@ -79,12 +73,6 @@ __device__ __forceinline__ const bf16* stage_base(const bf16* __restrict__ gsrc,
   int grow = row0 + row;
   if (MGUARD) grow = grow < rows_total ? grow : rows_total - 1;
   return gsrc + (int64_t)grow * ldg + chunk * 8;
-}
-
-__device__ __forceinline__ void glds16(const bf16* g, char* lds_dst) {
-  typedef const __attribute__((address_space(1))) unsigned int* gp_t;
-  typedef __attribute__((address_space(3))) unsigned int* lp_t;
-  __builtin_amdgcn_global_load_lds((gp_t)(const void*)g, (lp_t)(void*)lds_dst, 16, 0, 0);
 }
 
 __device__ __forceinline__ bf16x8_t lds_frag8p(const char* base, int byte_off) {
@@ -118,13 +106,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
 
   const int mt = MGUARD ? (M + BM - 1) / BM : M / BM;
   const int nt = N / BN;
-  const int nwg = mt * nt;
-  int wg = blockIdx.x;
-  {  // XCD-aware bijective remap (T1)
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, mt * nt);
   const int m0 = (wg / nt) * BM;
   const int n0 = (wg % nt) * BN;
   const int wm = (wave >> 2);  // 0..1
@@ -249,24 +231,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           const int n = n0 + wn * 64 + 16 * ni + lo;
-          float vpre = acc[pr][mi][ni][r];
-          if (HAS_BIAS) vpre += bias[n];
-          if (SAVE_PRE) Z[(int64_t)m * N + n] = f2bf(vpre);
-          float vy;
-          if (GRADM) {
-            // dX epilogue fused with the activation backward: res carries
-            // the saved pre-activation z; vy = (dy @ W) * act'(z)
-            vy = vpre * act_grad(bf2f(res[(int64_t)m * N + n]), ACT);
-          } else {
-            vy = act_fwd(vpre, ACT);
-            if (HAS_RES) vy += bf2f(res[(int64_t)m * N + n]);
-          }
-          Y[(int64_t)m * N + n] = f2bf(vy);
-          if (FP8O) {
-            // delayed-scaled e4m3 copy (consumed by the fp8 dX GEMM)
-            tmax = fmaxf(tmax, fabsf(vy));
-            Y8[(int64_t)m * N + n] = cvt_e4m3(vy * rs8);
-          }
+          gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE_PRE, GRADM, FP8O>(
+              acc[pr][mi][ni][r], m, n, N, bias, res, Y, Z, Y8, rs8, &tmax);
         }
       }
     }
@@ -283,106 +249,71 @@ bool gemm8p_supported(int64_t M, int64_t N, int64_t K) {
   return M >= 1 && (N % BN == 0) && (K % BK == 0) && K >= 2 * BK;
 }
 
-torch::Tensor gemm_nt_8p_gradact(torch::Tensor dy, torch::Tensor wt, torch::Tensor z,
-                                 std::string act) {
-  // dz = (dy @ wt^T as NT on pre-transposed wt [in_f, out_f]) * act'(z) —
-  // the dX GEMM of an activated linear with the activation backward fused
-  // into the epilogue (saves the separate act_bwd elementwise pass).
+namespace {
+
+// One launch of a gemm_nt_8p_kernel instantiation: 160 KiB of LDS (the full
+// CU), one workgroup per 256x256 output tile.
+template <auto Kernel>
+void launch_8p(const torch::Tensor& x, const torch::Tensor& w, const float* biasp,
+               const bf16* resp, torch::Tensor& y, bf16* zp, unsigned char* y8p = nullptr,
+               const float* scale8p = nullptr, unsigned int* amaxp = nullptr) {
+  const int M = x.size(0), K = x.size(1), N = w.size(0);
+  constexpr size_t shmem = 10 * HALF_BYTES;
+  const int mt = (M + BM - 1) / BM;
+  launch_lds<Kernel>(dim3(mt * (N / BN)), dim3(NTHREADS), shmem, shmem,
+                     at::hip::getCurrentHIPStream(), reinterpret_cast<const bf16*>(x.data_ptr()),
+                     reinterpret_cast<const bf16*>(w.data_ptr()), biasp, resp,
+                     reinterpret_cast<bf16*>(y.data_ptr()), zp, M, N, K, y8p, scale8p, amaxp);
+}
+
+// dz = (dy @ wt^T as NT on pre-transposed wt [in_f, out_f]) * act'(z) —
+// the dX GEMM of an activated linear with the activation backward fused
+// into the epilogue (saves the separate act_bwd elementwise pass).  With
+// scale8/amax also the fused delayed-scaled e4m3 emission of dz (producer of
+// the downstream fp8 dX GEMM); returns {dz bf16} or {dz bf16, dz8 e4m3 bytes}.
+std::vector<torch::Tensor> gradact_8p(torch::Tensor dy, torch::Tensor wt, torch::Tensor z,
+                                      const std::string& act,
+                                      c10::optional<torch::Tensor> scale8,
+                                      c10::optional<torch::Tensor> amax) {
   const int M = dy.size(0), K = dy.size(1), N = wt.size(0);
   TORCH_CHECK(dy.is_contiguous() && wt.is_contiguous() && z.is_contiguous());
   TORCH_CHECK(wt.size(1) == K && z.size(0) == M && z.size(1) == N);
   TORCH_CHECK(gemm8p_supported(M, N, K));
-  int act_code = ACT_NONE;
-  if (act == "gelu") act_code = ACT_GELU;
-  else if (act == "gelu_tanh") act_code = ACT_GELU_TANH;
-  else if (act == "quickgelu") act_code = ACT_QUICKGELU;
-  else TORCH_CHECK(false, "gradact needs an activation, got ", act);
+  TORCH_CHECK(!act.empty(), "gradact needs an activation, got ", act);
+  const bool fp8 = scale8.has_value();
   auto y = torch::empty({M, N}, dy.options());
-  auto stream = at::hip::getCurrentHIPStream();
-  const size_t shmem = 10 * HALF_BYTES;
-  const bool mguard = (M % BM) != 0;
-  const int mt = (M + BM - 1) / BM;
-#define LAUNCH_GRAD(ACTC, MG)                                                              \
-  do {                                                                                     \
-    auto kfn = gemm_nt_8p_kernel<ACTC, false, true, false, MG, true>;                      \
-    static bool attr_g_##ACTC##MG = [&] {                                                  \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                              \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);         \
-      return true;                                                                         \
-    }();                                                                                   \
-    (void)attr_g_##ACTC##MG;                                                               \
-    hipLaunchKernelGGL(kfn, dim3(mt * (N / BN)), dim3(NTHREADS), shmem, stream,            \
-                       reinterpret_cast<const bf16*>(dy.data_ptr()),                       \
-                       reinterpret_cast<const bf16*>(wt.data_ptr()), nullptr,              \
-                       reinterpret_cast<const bf16*>(z.data_ptr()),                        \
-                       reinterpret_cast<bf16*>(y.data_ptr()), nullptr, M, N, K,            \
-                       nullptr, nullptr, nullptr);                                         \
-  } while (0)
-#define DG(ACTC)                                                                           \
-  do {                                                                                     \
-    if (mguard) LAUNCH_GRAD(ACTC, true);                                                   \
-    else LAUNCH_GRAD(ACTC, false);                                                         \
-  } while (0)
-  switch (act_code) {
-    case ACT_GELU: DG(ACT_GELU); break;
-    case ACT_GELU_TANH: DG(ACT_GELU_TANH); break;
-    case ACT_QUICKGELU: DG(ACT_QUICKGELU); break;
-  }
-#undef DG
-#undef LAUNCH_GRAD
-  return y;
+  torch::Tensor y8;
+  if (fp8) y8 = torch::empty({M, N}, dy.options().dtype(torch::kUInt8));
+  unsigned char* y8p = fp8 ? y8.data_ptr<unsigned char>() : nullptr;
+  const float* scale8p = fp8 ? scale8->data_ptr<float>() : nullptr;
+  unsigned int* amaxp = fp8 ? reinterpret_cast<unsigned int*>(amax->data_ptr()) : nullptr;
+  const bf16* zp = reinterpret_cast<const bf16*>(z.data_ptr());
+  with_act(act_code(act), [&](auto act_c) {
+    with_flags(
+        [&](auto mg, auto fp8_c) {
+          constexpr int A = decltype(act_c)::value;
+          if constexpr (A != ACT_NONE)
+            launch_8p<gemm_nt_8p_kernel<A, false, true, false, decltype(mg)::value, true,
+                                        decltype(fp8_c)::value>>(dy, wt, nullptr, zp, y, nullptr,
+                                                                 y8p, scale8p, amaxp);
+        },
+        (M % BM) != 0, fp8);
+  });
+  if (fp8) return {y, y8};
+  return {y};
+}
+
+}  // namespace
+
+torch::Tensor gemm_nt_8p_gradact(torch::Tensor dy, torch::Tensor wt, torch::Tensor z,
+                                 std::string act) {
+  return gradact_8p(dy, wt, z, act, c10::nullopt, c10::nullopt)[0];
 }
 
 std::vector<torch::Tensor> gemm_nt_8p_gradact_fp8(torch::Tensor dy, torch::Tensor wt,
                                                   torch::Tensor z, std::string act,
                                                   torch::Tensor scale8, torch::Tensor amax) {
-  // gemm_nt_8p_gradact + fused delayed-scaled e4m3 emission of dz (producer
-  // of the downstream fp8 dX GEMM); returns {dz bf16, dz8 e4m3 bytes}.
-  const int M = dy.size(0), K = dy.size(1), N = wt.size(0);
-  TORCH_CHECK(dy.is_contiguous() && wt.is_contiguous() && z.is_contiguous());
-  TORCH_CHECK(wt.size(1) == K && z.size(0) == M && z.size(1) == N);
-  TORCH_CHECK(gemm8p_supported(M, N, K));
-  int act_code = ACT_NONE;
-  if (act == "gelu") act_code = ACT_GELU;
-  else if (act == "gelu_tanh") act_code = ACT_GELU_TANH;
-  else if (act == "quickgelu") act_code = ACT_QUICKGELU;
-  else TORCH_CHECK(false, "gradact needs an activation, got ", act);
-  auto y = torch::empty({M, N}, dy.options());
-  auto y8 = torch::empty({M, N}, dy.options().dtype(torch::kUInt8));
-  auto stream = at::hip::getCurrentHIPStream();
-  const size_t shmem = 10 * HALF_BYTES;
-  const bool mguard = (M % BM) != 0;
-  const int mt = (M + BM - 1) / BM;
-#define LAUNCH_GRAD8(ACTC, MG)                                                             \
-  do {                                                                                     \
-    auto kfn = gemm_nt_8p_kernel<ACTC, false, true, false, MG, true, true>;                \
-    static bool attr_g8_##ACTC##MG = [&] {                                                 \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                              \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);         \
-      return true;                                                                         \
-    }();                                                                                   \
-    (void)attr_g8_##ACTC##MG;                                                              \
-    hipLaunchKernelGGL(kfn, dim3(mt * (N / BN)), dim3(NTHREADS), shmem, stream,            \
-                       reinterpret_cast<const bf16*>(dy.data_ptr()),                       \
-                       reinterpret_cast<const bf16*>(wt.data_ptr()), nullptr,              \
-                       reinterpret_cast<const bf16*>(z.data_ptr()),                        \
-                       reinterpret_cast<bf16*>(y.data_ptr()), nullptr, M, N, K,            \
-                       y8.data_ptr<unsigned char>(), scale8.data_ptr<float>(),             \
-                       reinterpret_cast<unsigned int*>(amax.data_ptr()));                  \
-  } while (0)
-#define DG8(ACTC)                                                                          \
-  do {                                                                                     \
-    if (mguard) LAUNCH_GRAD8(ACTC, true);                                                  \
-    else LAUNCH_GRAD8(ACTC, false);                                                        \
-  } while (0)
-  switch (act_code) {
-    case ACT_GELU: DG8(ACT_GELU); break;
-    case ACT_GELU_TANH: DG8(ACT_GELU_TANH); break;
-    case ACT_QUICKGELU: DG8(ACT_QUICKGELU); break;
-  }
-#undef DG8
-#undef LAUNCH_GRAD8
-  return {y, y8};
+  return gradact_8p(dy, wt, z, act, scale8, amax);
 }
 
 void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias_f32,
@@ -390,56 +321,16 @@ void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> b
                 c10::optional<torch::Tensor> z) {
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(gemm8p_supported(M, N, K));
-  int act_code = ACT_NONE;
-  if (act == "gelu") act_code = ACT_GELU;
-  else if (act == "gelu_tanh") act_code = ACT_GELU_TANH;
-  else if (act == "quickgelu") act_code = ACT_QUICKGELU;
-  else TORCH_CHECK(act.empty(), "unknown act ", act);
-  auto stream = at::hip::getCurrentHIPStream();
   const bf16* resp = residual ? reinterpret_cast<const bf16*>(residual->data_ptr()) : nullptr;
   const float* biasp = bias_f32 ? bias_f32->data_ptr<float>() : nullptr;
   bf16* zp = z ? reinterpret_cast<bf16*>(z->data_ptr()) : nullptr;
-  const size_t shmem = 10 * HALF_BYTES;  // 160 KiB (full CU LDS)
-  const bool mguard = (M % BM) != 0;
-  const int mt = (M + BM - 1) / BM;
-
-#define LAUNCH8P(ACTC, HB, HR, SP, MG)                                                     \
-  do {                                                                                     \
-    auto kfn = gemm_nt_8p_kernel<ACTC, HB, HR, SP, MG>;                                    \
-    static bool attr_set_##ACTC##HB##HR##SP##MG = [&] {                                    \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                              \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);         \
-      return true;                                                                         \
-    }();                                                                                   \
-    (void)attr_set_##ACTC##HB##HR##SP##MG;                                                 \
-    hipLaunchKernelGGL(kfn, dim3(mt * (N / BN)), dim3(NTHREADS), shmem, stream,            \
-                       reinterpret_cast<const bf16*>(x.data_ptr()),                        \
-                       reinterpret_cast<const bf16*>(w.data_ptr()), biasp, resp,           \
-                       reinterpret_cast<bf16*>(y.data_ptr()), zp, M, N, K,                 \
-                       nullptr, nullptr, nullptr);                                         \
-  } while (0)
-#define DISPATCH_MG(ACTC, HB, HR, SP)                                                      \
-  do {                                                                                     \
-    if (mguard) LAUNCH8P(ACTC, HB, HR, SP, true);                                          \
-    else LAUNCH8P(ACTC, HB, HR, SP, false);                                                \
-  } while (0)
-#define DISPATCH_ACT8P(HB, HR, SP)                                                         \
-  switch (act_code) {                                                                      \
-    case ACT_NONE: DISPATCH_MG(ACT_NONE, HB, HR, SP); break;                               \
-    case ACT_GELU: DISPATCH_MG(ACT_GELU, HB, HR, SP); break;                               \
-    case ACT_GELU_TANH: DISPATCH_MG(ACT_GELU_TANH, HB, HR, SP); break;                     \
-    case ACT_QUICKGELU: DISPATCH_MG(ACT_QUICKGELU, HB, HR, SP); break;                     \
-  }
-  const bool hb = bias_f32.has_value(), hr = residual.has_value(), sp = z.has_value();
-  if (hb && hr && sp) DISPATCH_ACT8P(true, true, true)
-  else if (hb && hr) DISPATCH_ACT8P(true, true, false)
-  else if (hb && sp) DISPATCH_ACT8P(true, false, true)
-  else if (hb) DISPATCH_ACT8P(true, false, false)
-  else if (hr && sp) DISPATCH_ACT8P(false, true, true)
-  else if (hr) DISPATCH_ACT8P(false, true, false)
-  else if (sp) DISPATCH_ACT8P(false, false, true)
-  else DISPATCH_ACT8P(false, false, false)
-#undef DISPATCH_ACT8P
-#undef DISPATCH_MG
-#undef LAUNCH8P
+  with_act(act_code(act), [&](auto act_c) {
+    with_flags(
+        [&](auto hb, auto hr, auto sp, auto mg) {
+          launch_8p<gemm_nt_8p_kernel<decltype(act_c)::value, decltype(hb)::value,
+                                      decltype(hr)::value, decltype(sp)::value,
+                                      decltype(mg)::value>>(x, w, biasp, resp, y, zp);
+        },
+        bias_f32.has_value(), residual.has_value(), z.has_value(), (M % BM) != 0);
+  });
 }

@@ -65,15 +65,13 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 typedef short bf16x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
 
 constexpr int BN = 256, BKW = 256, BMS = 64;  // n-tile, k-tile, m-step
 constexpr int NTHREADS = 512;
@@ -82,10 +80,6 @@ constexpr int UNIT_BYTES = 16384;   // one operand's 32x256 bf16 unit image
 constexpr int SLOT_BYTES = 2 * UNIT_BYTES;  // dz image + X image
 constexpr int RING = 5;             // ring slots (RING * 32 KiB of LDS)
 constexpr int GLDS_PER_UNIT = 4;    // per thread: 2 dz + 2 X
-
-__device__ __forceinline__ void raw_barrier_tn() {
-  asm volatile("s_barrier" ::: "memory");
-}
 
 // Counted wait: returns once at most the `newer` most recently issued
 // units of this wave are still in flight (vmcnt retires glds in order).
@@ -118,12 +112,6 @@ __device__ __forceinline__ void img_inv(int o, int& m, int& col) {
   col = nt * 16 + u * 8;
 }
 
-__device__ __forceinline__ void glds16t(const bf16* g, char* lds_dst) {
-  typedef const __attribute__((address_space(1))) unsigned int* gp_t;
-  typedef __attribute__((address_space(3))) unsigned int* lp_t;
-  __builtin_amdgcn_global_load_lds((gp_t)(const void*)g, (lp_t)(void*)lds_dst, 16, 0, 0);
-}
-
 template <bool ATOMIC, bool DBOUT = false, bool WSOUT = false>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
     const bf16* __restrict__ DZ, const bf16* __restrict__ X, float* __restrict__ C,
@@ -137,13 +125,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
   const int lo = lane & 15, hi = lane >> 4;
 
   const int nt_n = N / BN, nt_k = Kw / BKW;
-  const int nwg = nt_n * nt_k;
-  int wg = blockIdx.x;
-  {  // XCD-aware bijective remap
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, nt_n * nt_k);
   const int n0 = (wg / nt_k) * BN;
   const int k0 = (wg % nt_k) * BKW;
   const int wm = wave >> 2;  // 0..1 (n sub-position)
@@ -181,12 +163,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
   auto issue_unit = [&](char* slot) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      glds16t(pdz[j], slot + j * 8192 + ldst16);
+      glds16(pdz[j], slot + j * 8192 + ldst16);
       pdz[j] += (int64_t)BMU * N;
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      glds16t(px[j], slot + UNIT_BYTES + j * 8192 + ldst16);
+      glds16(px[j], slot + UNIT_BYTES + j * 8192 + ldst16);
       px[j] += (int64_t)BMU * Kw;
     }
   };
@@ -278,7 +260,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
           db_acc[0][mi] += s8;
         }
       }
-      raw_barrier_tn();
+      raw_barrier();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi)
@@ -322,7 +304,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
         }
       }
       before_bb();
-      raw_barrier_tn();
+      raw_barrier();
       after_bb();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -339,7 +321,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
     const int npro = nunit < RING ? nunit : RING;
     for (int u = 0; u < npro; ++u) issue_unit(smem + u * SLOT_BYTES);
     wait_units_in_flight(npro - 1);
-    raw_barrier_tn();
+    raw_barrier();
     int slot = 0;
     for (int u = 0; u < nunit; ++u) {
       char* sp = smem + slot * SLOT_BYTES;
@@ -361,7 +343,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
     // the ring is drained and every slot is free (see header)
     stage_reg_tail();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    raw_barrier_tn();
+    raw_barrier();
     for (int kh = 0; kh < 2; ++kh)
       consume_unit(smem + kh * SLOT_BYTES, [] {}, [] {});
   }
@@ -516,20 +498,11 @@ static torch::Tensor tn8p_run(torch::Tensor dz, torch::Tensor x, float* dbp, int
   }
   const size_t shmem = (size_t)RING * SLOT_BYTES;  // 160 KiB
 #define LAUNCH_TN(AT, DBO, WSO)                                                            \
-  do {                                                                                     \
-    auto kfn = gemm_tn_8p_kernel<AT, DBO, WSO>;                                            \
-    static bool attr_##AT##DBO##WSO = [&] {                                                \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                              \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);         \
-      return true;                                                                         \
-    }();                                                                                   \
-    (void)attr_##AT##DBO##WSO;                                                             \
-    hipLaunchKernelGGL(kfn, dim3(tiles, splitm), dim3(NTHREADS), shmem, stream,            \
-                       reinterpret_cast<const bf16*>(dz.data_ptr()),                       \
-                       reinterpret_cast<const bf16*>(x.data_ptr()),                        \
-                       WSO ? ws.data_ptr<float>() : C.data_ptr<float>(), M, N, Kw, chunk,  \
-                       dbp);                                                               \
-  } while (0)
+  launch_lds<gemm_tn_8p_kernel<AT, DBO, WSO>>(                                             \
+      dim3(tiles, splitm), dim3(NTHREADS), shmem, shmem, stream,                           \
+      reinterpret_cast<const bf16*>(dz.data_ptr()),                                        \
+      reinterpret_cast<const bf16*>(x.data_ptr()),                                         \
+      WSO ? ws.data_ptr<float>() : C.data_ptr<float>(), M, N, Kw, chunk, dbp)
   if (use_ws) {
     if (dbp) LAUNCH_TN(false, true, true);
     else LAUNCH_TN(false, false, true);

@@ -1,0 +1,187 @@
+// Shared pieces of the MFMA kernels (GEMMs and attention): device primitives
+// that several kernels use unchanged, the fused GEMM epilogue, and the host
+// helpers that pick a kernel instantiation and launch it.
+#pragma once
+
+#include <string>
+#include <type_traits>
+
+#include "common.h"
+
+#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
+
+// ---- device primitives -----------------------------------------------------
+
+// s_barrier alone: no s_waitcnt in front of it (unlike __syncthreads()), so
+// counted vmcnt waits keep staged tiles in flight across the barrier.
+__device__ __forceinline__ void raw_barrier() {
+  asm volatile("s_barrier" ::: "memory");
+}
+
+// 16-byte global -> LDS copy (global_load_lds): lane l's 16 B land at
+// lds_dst + l*16 of the wave's base, so lds_dst is wave-linear and any image
+// permutation goes on the per-lane SOURCE address.
+__device__ __forceinline__ void glds16(const bf16* g, char* lds_dst) {
+  // C-style casts perform the addrspace conversion (generic->AS1/AS3);
+  // reinterpret_cast refuses (same idiom as CK's c_style_pointer_cast)
+  typedef const __attribute__((address_space(1))) unsigned int* gp_t;
+  typedef __attribute__((address_space(3))) unsigned int* lp_t;
+  __builtin_amdgcn_global_load_lds((gp_t)(const void*)g, (lp_t)(void*)lds_dst, 16, 0, 0);
+}
+
+// XCD-aware bijective remap of the linear workgroup id (guide T1): the
+// hardware deals workgroups round-robin over the 8 XCDs, so XCD x gets the
+// contiguous run of tiles starting at its share of nwg — neighbouring tiles
+// share an L2.
+__device__ __forceinline__ int xcd_remap(int wg, int nwg) {
+  const int q = nwg / 8, r = nwg % 8;
+  const int xcd = wg % 8, idx = wg / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// Guarded 8-element load for head dims beyond 64: kernels are templated on
+// the PADDED head dim DP in {64, 96, 128} (d-fragments need multiples of 32)
+// and the runtime Dr (72, 80 pad to 96) guards ragged chunks — 8-element
+// chunks are all-in or all-out since every supported D is a multiple of 8.
+template <int DP>
+__device__ __forceinline__ bf16x8 ld8g(const bf16* p, int off, int Dr) {
+  if (DP == 64 || off + 8 <= Dr) return *reinterpret_cast<const bf16x8*>(p + off);
+  return bf16x8{};
+}
+
+// Block-format image for transposed fragment reads (the gemm_tn8p.hip
+// recipe): a [64 q][ND d] tile stored as [q-half (q>>5)][d16 (d>>4)]
+// [8 q-quads, evens first][4][16] — written from row-major registers with
+// ds_write_b128 (two vector writes per 16-d chunk instead of 16 scalar
+// transpose stores, which were 8-way bank-conflicted), and read as MFMA
+// B-fragments with batched ds_read_b64_tr_b16 at per-lane address
+// base + lane*8 B (mapping verified by ext.tr16_probe).
+template <int ND>
+__device__ __forceinline__ int boff(int q, int d) {
+  const int qp = (q >> 2) & 7;
+  const int qpos = (qp & 1) * 4 + (qp >> 1);
+  return (q >> 5) * (32 * ND) + (d >> 4) * 512 + qpos * 64 + (q & 3) * 16 + (d & 15);
+}
+
+typedef const __attribute__((address_space(3))) char* lds_cp;
+
+// 4 B-fragments (dt, dt+1, dt+2, dt+3) of one 32-contraction step from a
+// block image: 8 tr reads + lgkmcnt(0) in one asm (guide §5.7 form i).
+__device__ __forceinline__ void tr_frag_x4(lds_cp base, bf16x8 (&out)[4]) {
+  bf16x4 a0l, a0h, a1l, a1h, a2l, a2h, a3l, a3h;
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %8 offset:0\n\t"
+      "ds_read_b64_tr_b16 %1, %8 offset:512\n\t"
+      "ds_read_b64_tr_b16 %2, %8 offset:1024\n\t"
+      "ds_read_b64_tr_b16 %3, %8 offset:1536\n\t"
+      "ds_read_b64_tr_b16 %4, %8 offset:2048\n\t"
+      "ds_read_b64_tr_b16 %5, %8 offset:2560\n\t"
+      "ds_read_b64_tr_b16 %6, %8 offset:3072\n\t"
+      "ds_read_b64_tr_b16 %7, %8 offset:3584\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(a0l), "=&v"(a0h), "=&v"(a1l), "=&v"(a1h), "=&v"(a2l), "=&v"(a2h),
+        "=&v"(a3l), "=&v"(a3h)
+      : "v"(base)
+      : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  out[0] = __builtin_shufflevector(a0l, a0h, 0, 1, 2, 3, 4, 5, 6, 7);
+  out[1] = __builtin_shufflevector(a1l, a1h, 0, 1, 2, 3, 4, 5, 6, 7);
+  out[2] = __builtin_shufflevector(a2l, a2h, 0, 1, 2, 3, 4, 5, 6, 7);
+  out[3] = __builtin_shufflevector(a3l, a3h, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+__device__ __forceinline__ void tr_frag_x2(lds_cp base, bf16x8 (&out)[2]) {
+  bf16x4 a0l, a0h, a1l, a1h;
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %4 offset:0\n\t"
+      "ds_read_b64_tr_b16 %1, %4 offset:512\n\t"
+      "ds_read_b64_tr_b16 %2, %4 offset:1024\n\t"
+      "ds_read_b64_tr_b16 %3, %4 offset:1536\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(a0l), "=&v"(a0h), "=&v"(a1l), "=&v"(a1h)
+      : "v"(base)
+      : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  out[0] = __builtin_shufflevector(a0l, a0h, 0, 1, 2, 3, 4, 5, 6, 7);
+  out[1] = __builtin_shufflevector(a1l, a1h, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// ---- fused GEMM epilogue ---------------------------------------------------
+
+// One accumulator value of an NT GEMM at (m, n), already inside the bounds:
+//   vpre = acc (+ bias[n]);  Z = vpre (SAVE_PRE);
+//   Y = act(vpre) (+ res)                      forward
+//   Y = vpre * act'(res)                       GRADM: the dX GEMM of an
+//       activated linear with the activation backward fused in; res carries
+//       the saved pre-activation z
+//   Y8 = e4m3(Y * rs8), *tmax = max(*tmax, |Y|)   FP8O: delayed-scaled e4m3
+//       copy (consumed by the fp8 dX GEMM); the caller reduces tmax.
+template <int ACT, bool HAS_BIAS, bool HAS_RES, bool SAVE_PRE, bool GRADM = false,
+          bool FP8O = false>
+__device__ __forceinline__ void gemm_epilogue(float vpre, int m, int n, int N, const float* bias,
+                                              const bf16* res, bf16* Y, bf16* Z,
+                                              unsigned char* Y8 = nullptr, float rs8 = 1.f,
+                                              float* tmax = nullptr) {
+  if (HAS_BIAS) vpre += bias[n];
+  if (SAVE_PRE) Z[(int64_t)m * N + n] = f2bf(vpre);
+  float vy;
+  if (GRADM) {
+    vy = vpre * act_grad(bf2f(res[(int64_t)m * N + n]), ACT);
+  } else {
+    vy = act_fwd(vpre, ACT);
+    if (HAS_RES) vy += bf2f(res[(int64_t)m * N + n]);
+  }
+  Y[(int64_t)m * N + n] = f2bf(vy);
+  if (FP8O) {
+    *tmax = fmaxf(*tmax, fabsf(vy));
+    Y8[(int64_t)m * N + n] = cvt_e4m3(vy * rs8);
+  }
+}
+
+// ---- host: kernel selection and launch -------------------------------------
+
+// activation name -> ACT_* code ("" = none); throws on an unknown name
+// (elementwise.hip)
+int act_code(const std::string& act);
+
+// Run-time values -> template arguments. with_act calls f with a
+// std::integral_constant<int, ACT_*>; with_flags calls f with one
+// std::true_type / std::false_type per bool, in order. Read them back with
+// decltype(c)::value.
+template <typename F>
+void with_act(int act, F&& f) {
+  switch (act) {
+    case ACT_NONE: return f(std::integral_constant<int, ACT_NONE>{});
+    case ACT_GELU: return f(std::integral_constant<int, ACT_GELU>{});
+    case ACT_GELU_TANH: return f(std::integral_constant<int, ACT_GELU_TANH>{});
+    case ACT_QUICKGELU: return f(std::integral_constant<int, ACT_QUICKGELU>{});
+  }
+  TORCH_CHECK(false, "bad activation code ", act);
+}
+
+template <typename F>
+void with_flags(F&& f) {
+  f();
+}
+template <typename F, typename... Rest>
+void with_flags(F&& f, bool b, Rest... rest) {
+  if (b) with_flags([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+  else with_flags([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+
+// Launches Kernel with `shmem` bytes of dynamic LDS. Before its first launch
+// each kernel gets its dynamic-LDS limit raised to `shmem_limit` (>= every
+// shmem it will be launched with); a refusal surfaces here instead of as a
+// failed launch later.
+template <auto Kernel, typename... Args>
+void launch_lds(dim3 grid, dim3 block, size_t shmem, size_t shmem_limit, hipStream_t stream,
+                Args... args) {
+  static const bool raised = [&] {
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)shmem_limit));
+    return true;
+  }();
+  (void)raised;
+  hipLaunchKernelGGL(Kernel, grid, block, shmem, stream, args...);
+}

@@ -30,7 +30,6 @@ setup(
                 "jimm_amd/csrc/attention_bwd.hip",
                 "jimm_amd/csrc/attention_bwd_fused.hip",
                 "jimm_amd/csrc/gemm.hip",
-                "jimm_amd/csrc/gemm256.hip",
                 "jimm_amd/csrc/gemm8p.hip",
                 "jimm_amd/csrc/gemm_tn8p.hip",
                 "jimm_amd/csrc/losses.hip",

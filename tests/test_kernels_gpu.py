@@ -231,18 +231,51 @@ def test_attn_bwd(causal):
 
 
 # ---------------------------------------------------------------------------
+# (M, N, K, act, has_bias, has_res); z is saved where there is an activation
+_LINEAR_CASES = [
+    (256, 768, 768, "", True, False),
+    (197 * 4, 2304, 768, "", True, False),      # fused QKV (K4)
+    (512, 3072, 768, "gelu", True, False),       # fc1+gelu (K7)
+    (512, 768, 3072, "", True, True),            # fc2+residual (K8)
+    (100, 512, 2048, "quickgelu", True, False),  # CLIP text fc1, ragged M
+    (1000, 1000, 768, "", True, False),          # ragged N (classifier-ish)
+    (512, 256, 64, "", True, False),             # K = 64: runs the 128-tile glds kernel
+    (1024, 768, 768, "gelu", True, False),
+    (256, 2304, 768, "", True, False),
+    (512, 768, 3072, "quickgelu", True, False),
+    # 128-tile glds kernel, 6 workgroups: XCD remap with fewer workgroups than XCDs
+    (256, 384, 128, "quickgelu", True, True),
+    # 8-phase, 3 K-tiles (the B-slot rotation wraps), two M tiles, the second ragged
+    (300, 512, 192, "", True, False),
+    (130, 72, 64, "gelu_tanh", True, False),     # generic kernel, both edges ragged
+]
+# One smallest shape per forward GEMM kernel, crossed with every (bias,
+# residual, save_z) combination: each combination is its own kernel
+# instantiation, picked by the host dispatch from three run-time flags.
+_LINEAR_CASES += [
+    (M, N, K, "gelu" if save_z else "", has_bias, has_res)
+    for (M, N, K) in [
+        (256, 256, 128),  # 8-phase (K = 128 is its minimum)
+        (100, 256, 128),  # 8-phase, ragged M
+        (128, 128, 64),   # 128-tile glds kernel: one workgroup, one K tile
+        (100, 200, 64),   # 128-tile generic kernel
+    ]
+    for has_bias in (False, True)
+    for has_res in (False, True)
+    for save_z in (False, True)
+]
+
+
+def _linear_id(M, N, K, act, has_bias, has_res):
+    # cases with a bias keep the ids they had before has_bias existed
+    return f"{M}-{N}-{K}-{act}-{has_res}" if has_bias else f"{M}-{N}-{K}-{act}-nobias-{has_res}"
+
+
 @pytest.mark.parametrize(
-    "M,N,K,act,has_res",
-    [
-        (256, 768, 768, "", False),
-        (197 * 4, 2304, 768, "", False),      # fused QKV (K4)
-        (512, 3072, 768, "gelu", False),       # fc1+gelu (K7)
-        (512, 768, 3072, "", True),            # fc2+residual (K8)
-        (100, 512, 2048, "quickgelu", False),  # CLIP text fc1, ragged M
-        (1000, 1000, 768, "", False),          # ragged N (classifier-ish)
-    ],
+    "M,N,K,act,has_bias,has_res",
+    [pytest.param(*c, id=_linear_id(*c)) for c in _LINEAR_CASES],
 )
-def test_linear_fwd_mfma(M, N, K, act, has_res):
+def test_linear_fwd_mfma(M, N, K, act, has_bias, has_res):
     import os
 
     if os.environ.get("JIMM_AMD_GEMM", "hip") != "hip":
@@ -252,17 +285,51 @@ def test_linear_fwd_mfma(M, N, K, act, has_res):
 
     x = torch.randn(M, K, device=dev()).bfloat16()
     w = (torch.randn(N, K, device=dev()) / math.sqrt(K)).bfloat16()
-    bias = torch.randn(N, device=dev()).bfloat16()
+    bias = torch.randn(N, device=dev()).bfloat16() if has_bias else None
     res = torch.randn(M, N, device=dev()).bfloat16() if has_res else None
     assert EXT.gemm_supported(M, N, K, str(x.dtype))
-    y, z = EXT.linear_fwd(x, w, bias, act, res, bool(act))
-    ref_pre = x.float() @ w.float().t() + bias.float()
+    y, z = EXT.linear_fwd(x, w, bias, act, res, bool(act))  # save_z where activated
+    ref_pre = x.float() @ w.float().t()
+    if has_bias:
+        ref_pre = ref_pre + bias.float()
     ref = Fn._act(ref_pre, act or None)
     if has_res:
         ref = ref + res.float()
     assert rel_err(y, ref) < 2e-2, rel_err(y, ref)
     if act:
         assert rel_err(z, ref_pre) < 2e-2
+    else:
+        assert z is None
+
+
+@pytest.mark.parametrize("act", ["gelu", "gelu_tanh", "quickgelu"])
+@pytest.mark.parametrize("M,N,K", [(256, 256, 128), (100, 256, 128)])
+def test_gemm_gradact(M, N, K, act):
+    """dX GEMM with the activation backward fused into the epilogue:
+    (dy @ wt^T) * act'(z), plain and with the fused e4m3 emission."""
+    torch.manual_seed(0)
+    import jimm_amd.ops.functional as Fn
+
+    dy = torch.randn(M, K, device=dev()).bfloat16()
+    wt = (torch.randn(N, K, device=dev()) / math.sqrt(K)).bfloat16()
+    z = torch.randn(M, N, device=dev()).bfloat16()
+    zf = z.float().requires_grad_(True)
+    (dact,) = torch.autograd.grad(Fn._act(zf, act).sum(), zf)
+    ref = (dy.float() @ wt.float().t()) * dact
+
+    y = EXT.gemm_nt_8p_gradact(dy, wt, z, act)
+    assert rel_err(y, ref) < 2e-2, rel_err(y, ref)
+
+    scale = (ref.abs().max() / 448.0).reshape(1)
+    amax = torch.zeros(1, device=dev(), dtype=torch.float32)
+    y2, y8 = EXT.gemm_nt_8p_gradact_fp8(dy, wt, z, act, scale, amax)
+    assert torch.equal(y2, y)
+    deq = y8.view(torch.float8_e4m3fn).float() * scale
+    # half an e4m3 ulp at the top binade is 16/448
+    assert rel_err(deq, y.float()) < 0.04, rel_err(deq, y.float())
+    # the kernel takes the max before the bf16 rounding (which moves a value by <= 2^-9)
+    ymax = y.float().abs().max().item()
+    assert abs(amax.item() - ymax) <= 2.0 ** -8 * ymax, (amax.item(), ymax)
 
 
 # ---------------------------------------------------------------------------
@@ -400,31 +467,6 @@ def test_colsum():
 
 
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize(
-    "M,N,K,act",
-    [
-        (512, 256, 64, ""),            # smallest 256-tile shape
-        (1024, 768, 768, "gelu"),      # routes to gemm256 fast path
-        (256, 2304, 768, ""),
-        (512, 768, 3072, "quickgelu"),
-    ],
-)
-def test_gemm256(M, N, K, act):
-    """256x256-tile MFMA GEMM (csrc/gemm256.hip) vs fp32 reference."""
-    torch.manual_seed(0)
-    import jimm_amd.ops.functional as Fn
-
-    x = torch.randn(M, K, device=dev()).bfloat16()
-    w = (torch.randn(N, K, device=dev()) / math.sqrt(K)).bfloat16()
-    bias = torch.randn(N, device=dev()).bfloat16()
-    y, z = EXT.linear_fwd(x, w, bias, act, None, bool(act))
-    ref_pre = x.float() @ w.float().t() + bias.float()
-    ref = Fn._act(ref_pre, act or None)
-    assert rel_err(y, ref) < 2e-2, rel_err(y, ref)
-    if act:
-        assert rel_err(z, ref_pre) < 2e-2
-
-
 @pytest.mark.parametrize(
     "M,N,K",
     [
