@@ -29,7 +29,7 @@ FLOOR_STEP_VIT_B1024 = 5500  # img/s (r02 final: 5753)
 # in-house GEMM floors on the b1024 model shapes (median TF/s, -10%)
 FLOORS_GEMM = {  # (M, N, K, act): fwd_tf
     (201728, 2304, 768, ""): 790,
-    (201728, 3072, 768, "gelu"): 600,
+    (201728, 3072, 768, "gelu"): 624,  # hardware-rcp erf + hoisted bias: 0.9 x measured 695 / 696 / 694
     (201728, 768, 3072, ""): 890,
 }
 FLOORS_DW = {  # (M, N, K): tf (staging ring + round-aware splits; 0.9 x measured 953 / 980 / 970)

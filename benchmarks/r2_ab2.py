@@ -1,10 +1,11 @@
 """Round-2 follow-up A/Bs at config-5 shapes (M=128*577):
-  1. fc2-dX gradact: fused epilogue (bf16 / fp8-emit) vs plain GEMM +
-     separate act_bwd (+ fp8_cast) passes.
+  1. fc2-dX gradact: fused epilogue (bf16 / fp8-emit) vs the gradmul
+     epilogue (saved fp16 derivative) vs plain GEMM + separate act_bwd
+     (+ fp8_cast) passes; fc1 forward in the three save modes.
   2. dW gemm_tn_8p across the 4 block shapes (run under different
      JIMM_AMD_DW_SPLITM to sweep the split factor — it is read once).
   3. layernorm_fwd vs layernorm_fwd_fp8 at (M, 1024).
-Run on the GPU box: python benchmarks/r2_ab2.py [gradact|dw|ln|all]
+Run on the GPU box: python benchmarks/r2_ab2.py [gradact [M N K]|dw|ln|all]
 """
 
 import os
@@ -32,17 +33,25 @@ def t_ms(fn, iters=20):
     return s.elapsed_time(e) / iters
 
 
-def gradact():
+def gradact(m=M, n=4096, k=1024, rounds=3):
+    """fc2-dX and fc1-forward epilogue variants at (m, n, k), interleaved in
+    one process, `rounds` times over. Default: the config-5 (ViT-L) shape;
+    `gradact 201728 3072 768` is ViT-B at batch 1024."""
     ext = _backend.ext()
-    dy = torch.randn(M, 1024, device="cuda").bfloat16()
-    wt = torch.randn(4096, 1024, device="cuda").bfloat16() / 30
-    z = torch.randn(M, 4096, device="cuda").bfloat16()
+    dy = torch.randn(m, k, device="cuda").bfloat16()
+    wt = torch.randn(n, k, device="cuda").bfloat16() / 30
+    z = torch.randn(m, n, device="cuda").bfloat16()
+    g = torch.rand(m, n, device="cuda").half()
+    b = torch.randn(n, device="cuda").bfloat16()
     s8 = torch.ones(1, device="cuda")
     am = torch.zeros(1, device="cuda")
-    tf = 2.0 * M * 4096 * 1024 / 1e12
+    tf = 2.0 * m * n * k / 1e12
 
     def fused():
         return ext.gemm_nt_8p_gradact(dy, wt, z, "gelu")
+
+    def gradmul():
+        return ext.gemm_nt_8p_gradmul(dy, wt, g)
 
     def fused8():
         return ext.gemm_nt_8p_gradact_fp8(dy, wt, z, "gelu", s8, am)
@@ -56,10 +65,22 @@ def gradact():
         dz = ext.act_bwd(df, z, "gelu")
         return ext.fp8_cast(dz, s8, am)
 
-    for name, fn in (("fused", fused), ("fused+e4m3", fused8),
-                     ("plain+actbwd", plain), ("plain+actbwd+cast", plain8)):
-        ms = t_ms(fn)
-        print(f"gradact {name:18s} {ms:7.3f} ms  {tf / (ms * 1e-3):6.0f} TF/s")
+    rows = [("fused", fused), ("gradmul", gradmul), ("fused+e4m3", fused8),
+            ("plain+actbwd", plain),
+            # what gradmul should approach: the residual-add epilogue reads the
+            # same bytes and does an add where gradmul does a multiply
+            ("plain GEMM", lambda: ext.linear_fwd(dy, wt, None, "", None, False)),
+            ("residual add", lambda: ext.linear_fwd(dy, wt, None, "", z, False)),
+            # fc1 forward (bias + gelu) in the three save modes
+            ("fwd save none", lambda: ext.linear_fwd(dy, wt, b, "gelu", None, False)),
+            ("fwd save z", lambda: ext.linear_fwd(dy, wt, b, "gelu", None, True)),
+            ("fwd save g", lambda: ext.linear_fwd_actgrad(dy, wt, b, "gelu", None))]
+    if hasattr(ext, "fp8_cast"):
+        rows.append(("plain+actbwd+cast", plain8))
+    for rnd in range(rounds):
+        for name, fn in rows:
+            ms = t_ms(fn)
+            print(f"gradact r{rnd} {name:18s} {ms:7.3f} ms  {tf / (ms * 1e-3):6.0f} TF/s", flush=True)
 
 
 def dw():
@@ -89,7 +110,7 @@ def ln():
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     if which in ("gradact", "all"):
-        gradact()
+        gradact(*(int(v) for v in sys.argv[2:5]))
     if which in ("dw", "all"):
         dw()
     if which in ("ln", "all"):

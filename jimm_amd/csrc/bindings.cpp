@@ -62,6 +62,11 @@ torch::Tensor tr16_probe(torch::Tensor src, int64_t mode);
 std::vector<torch::Tensor> linear_fwd(torch::Tensor x, torch::Tensor w,
                                       c10::optional<torch::Tensor> bias, std::string act,
                                       c10::optional<torch::Tensor> residual, bool save_z);
+std::vector<torch::Tensor> linear_fwd_actgrad(torch::Tensor x, torch::Tensor w,
+                                              c10::optional<torch::Tensor> bias,
+                                              std::string act,
+                                              c10::optional<torch::Tensor> residual);
+torch::Tensor gemm_nt_8p_gradmul(torch::Tensor dy, torch::Tensor wt, torch::Tensor g);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd, "LayerNorm forward (K3)");
@@ -110,4 +115,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xent_rows_bwd", &xent_rows_bwd, "fused softmax-CE backward (K13)");
   m.def("sigmoid_loss_ew", &sigmoid_loss_ew, "SigLIP sigmoid loss + dLogits (K13)");
   m.def("linear_fwd", &linear_fwd, "MFMA GEMM + fused epilogue (K4/K6/K7/K8)");
+  m.def("linear_fwd_actgrad", &linear_fwd_actgrad,
+        "linear_fwd that returns (y, fp16 act'(pre)) instead of the pre-activation",
+        py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("act"),
+        py::arg("residual") = py::none());
+  m.def("gemm_nt_8p_gradmul", &gemm_nt_8p_gradmul,
+        "dX GEMM times a saved fp16 activation derivative");
 }

@@ -56,43 +56,93 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
 #define ACT_GELU_TANH 2
 #define ACT_QUICKGELU 3
 
-// Fast erf (Abramowitz-Stegun 7.1.26, |err| <= 1.5e-7 — below bf16
-// resolution): ~12 VALU + 1 v_rcp + 1 v_exp vs libm erff's branchy
-// polynomial, which measured ~75 lane-cycles/element as a GEMM epilogue.
+// Hardware reciprocal (one v_rcp_f32, 1 ulp). `1.0f / x` and __frcp_rn(x)
+// both compile to the IEEE division sequence (2 v_div_scale, v_rcp, an fma
+// chain, v_div_fmas, v_div_fixup: ~10 VALU per element), which a GEMM
+// epilogue cannot afford and a bf16/fp16 result cannot see.
+__device__ __forceinline__ float fast_rcpf(float x) { return __builtin_amdgcn_rcpf(x); }
+
+// Fast erfc tail (Abramowitz-Stegun 7.1.26): for ax >= 0 and
+// ex = exp(-ax^2), erfc(ax) ~= t*p(t)*ex with t = 1/(1 + 0.3275911 ax).
+// The formula itself is good to 1.5e-7 (1.4e-7 in fp64 over [-6, 6]). In
+// fp32 the rounding of the Horner chain and of the final 1 - q dominates:
+// an fp32 simulation over 3e6 points gives 5.8e-7 with a correctly rounded
+// reciprocal and exp, and 8.4e-7 with both off by a whole ulp in the worst
+// direction (t*p(t) has slope <= 3.5 in t, so 1 ulp of t <= 1 moves the
+// result by at most 2.1e-7). Bound: |err| <= 1e-6 on erf, against 2^-9 for
+// a bf16 and 2^-12 for an fp16 result near 1. 7 VALU + 1 v_rcp_f32; the
+// caller supplies the exp.
+__device__ __forceinline__ float fast_erfc_tail(float ax, float ex) {
+  const float t = fast_rcpf(fmaf(0.3275911f, ax, 1.0f));
+  float p = 1.061405429f;
+  p = fmaf(p, t, -1.453152027f);
+  p = fmaf(p, t, 1.421413741f);
+  p = fmaf(p, t, -0.284496736f);
+  p = fmaf(p, t, 0.254829592f);
+  return p * t * ex;
+}
+
+// erf(x), |err| <= 1e-6 (see fast_erfc_tail): ~12 VALU + 1 v_rcp + 1 v_exp
+// vs libm erff's branchy polynomial, which measured ~75 lane-cycles/element
+// as a GEMM epilogue.
 __device__ __forceinline__ float fast_erff(float x) {
   const float ax = fabsf(x);
-  const float t = __frcp_rn(1.0f + 0.3275911f * ax);
-  float p = 1.061405429f;
-  p = p * t - 1.453152027f;
-  p = p * t + 1.421413741f;
-  p = p * t - 0.284496736f;
-  p = p * t + 0.254829592f;
-  const float e = 1.0f - p * t * __expf(-ax * ax);
-  return copysignf(e, x);
+  return copysignf(1.0f - fast_erfc_tail(ax, __expf(-ax * ax)), x);
 }
 
 __device__ __forceinline__ float fast_tanhf(float x) {
   // tanh(x) = 1 - 2/(exp(2x)+1); clamp avoids exp overflow (|x|>10 -> +-1)
   const float cx = fminf(fmaxf(x, -10.0f), 10.0f);
-  return 1.0f - 2.0f / (__expf(2.0f * cx) + 1.0f);
+  return 1.0f - 2.0f * fast_rcpf(__expf(2.0f * cx) + 1.0f);
 }
 
-__device__ __forceinline__ float act_fwd(float x, int act) {
+// act(x) and act'(x) from shared sub-expressions: one v_exp_f32 and one
+// v_rcp_f32 per element for every activation. act_fwd and act_grad below
+// are this function with one output dropped (the compiler removes the dead
+// half), so the three always agree and a forward GEMM that also saves the
+// derivative returns bitwise the same y as one that does not.
+//   erf-GELU: x*Phi(x); derivative Phi(x) + x*phi(x). The erfc tail's
+//     exp(-(x/sqrt2)^2) IS the pdf's exp(-x^2/2), so the derivative costs
+//     two more operations than the forward.
+//   tanh-GELU and QuickGELU: the derivative reuses the tanh / sigmoid.
+__device__ __forceinline__ float act_fwd_grad(float x, int act, float* g) {
   switch (act) {
-    case ACT_GELU:
-      return 0.5f * x * (1.0f + fast_erff(x * 0.70710678118654752440f));
+    case ACT_GELU: {
+      const float u = x * 0.70710678118654752440f;
+      const float au = fabsf(u);
+      const float ex = __expf(-au * au);  // exp(-x^2/2)
+      const float s = 1.0f + copysignf(1.0f - fast_erfc_tail(au, ex), u);  // 2*Phi(x)
+      *g = fmaf(x, 0.3989422804014327f * ex, 0.5f * s);
+      return 0.5f * x * s;
+    }
     case ACT_GELU_TANH: {
-      float x3 = x * x * x;
-      float t = fast_tanhf(0.7978845608028654f * (x + 0.044715f * x3));
+      const float x2 = x * x;
+      const float x3 = x2 * x;
+      const float t = fast_tanhf(0.7978845608028654f * (x + 0.044715f * x3));
+      const float dinner = 0.7978845608028654f * (1.0f + 3.0f * 0.044715f * x2);
+      *g = 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * dinner;
       return 0.5f * x * (1.0f + t);
     }
     case ACT_QUICKGELU: {
-      float s = 1.0f / (1.0f + __expf(-1.702f * x));
+      const float s = fast_rcpf(1.0f + __expf(-1.702f * x));
+      *g = s + 1.702f * x * s * (1.0f - s);
       return x * s;
     }
     default:
+      *g = 1.0f;
       return x;
   }
+}
+
+__device__ __forceinline__ float act_fwd(float x, int act) {
+  float g;
+  return act_fwd_grad(x, act, &g);
+}
+
+__device__ __forceinline__ float act_grad(float x, int act) {
+  float g;
+  act_fwd_grad(x, act, &g);
+  return g;
 }
 
 // e4m3 (OCP) converts on the hardware v_cvt_pk_fp8_f32 pipe. The HIP
@@ -108,30 +158,6 @@ __device__ __forceinline__ unsigned short cvt2_e4m3(float a, float b) {
 
 __device__ __forceinline__ unsigned char cvt_e4m3(float a) {
   return (unsigned char)(cvt2_e4m3(a, 0.f) & 0xff);
-}
-
-__device__ __forceinline__ float act_grad(float x, int act) {
-  switch (act) {
-    case ACT_GELU: {
-      // d/dx [x * Phi(x)] = Phi(x) + x * phi(x)
-      float cdf = 0.5f * (1.0f + fast_erff(x * 0.70710678118654752440f));
-      float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
-      return cdf + x * pdf;
-    }
-    case ACT_GELU_TANH: {
-      float x2 = x * x;
-      float inner = 0.7978845608028654f * (x + 0.044715f * x * x2);
-      float t = fast_tanhf(inner);
-      float dinner = 0.7978845608028654f * (1.0f + 3.0f * 0.044715f * x2);
-      return 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * dinner;
-    }
-    case ACT_QUICKGELU: {
-      float s = 1.0f / (1.0f + __expf(-1.702f * x));
-      return s + 1.702f * x * s * (1.0f - s);
-    }
-    default:
-      return 1.0f;
-  }
 }
 
 // ---- vectorized load/store helpers (G13: hipcc does not auto-vectorize

@@ -67,10 +67,10 @@ __device__ __forceinline__ bf16x8_t lds_read_frag(const short* base, int row, in
   return *reinterpret_cast<const bf16x8_t*>(reinterpret_cast<const char*>(base) + byte);
 }
 
-template <int ACT, bool HAS_BIAS, bool HAS_RES, bool SAVE_PRE>
+template <int ACT, bool HAS_BIAS, bool HAS_RES, int SAVE>
 __global__ __launch_bounds__(256) void gemm_nt_fast_kernel(
-    const bf16* __restrict__ X, const bf16* __restrict__ W, const float* __restrict__ bias,
-    const bf16* __restrict__ res, bf16* __restrict__ Y, bf16* __restrict__ Z,
+    const bf16* __restrict__ X, const bf16* __restrict__ W, const void* __restrict__ bias,
+    int bias_bf16, const bf16* __restrict__ res, bf16* __restrict__ Y, bf16* __restrict__ Z,
     int M, int N, int K) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   short* smem_s = reinterpret_cast<short*>(smem);
@@ -118,7 +118,13 @@ __global__ __launch_bounds__(256) void gemm_nt_fast_kernel(
     __syncthreads();  // also drains the in-flight global_load_lds (vmcnt 0)
   }
 
-  // epilogue: C rows = m (hi*4+r of each 16-fragment), col = n (lo)
+  // epilogue: C rows = m (hi*4+r of each 16-fragment), col = n (lo); a lane
+  // owns 4 columns, so its 4 bias values are loaded once
+  float bv[4] = {};
+  if (HAS_BIAS) {
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) bv[ni] = load_bias(bias, n0 + wn + 16 * ni + lo, bias_bf16);
+  }
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
@@ -127,7 +133,7 @@ __global__ __launch_bounds__(256) void gemm_nt_fast_kernel(
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const int n = n0 + wn + 16 * ni + lo;
-        gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE_PRE>(acc[mi][ni][r], m, n, N, bias, res, Y, Z);
+        gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE>(acc[mi][ni][r], m, n, N, bv[ni], res, Y, Z);
       }
     }
   }
@@ -137,10 +143,10 @@ __global__ __launch_bounds__(256) void gemm_nt_fast_kernel(
 // generic (ragged) path — guarded staging, padded LDS, register staging
 // ---------------------------------------------------------------------------
 
-template <int ACT, bool HAS_BIAS, bool HAS_RES, bool SAVE_PRE>
+template <int ACT, bool HAS_BIAS, bool HAS_RES, int SAVE>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(
-    const bf16* __restrict__ X, const bf16* __restrict__ W, const float* __restrict__ bias,
-    const bf16* __restrict__ res, bf16* __restrict__ Y, bf16* __restrict__ Z,
+    const bf16* __restrict__ X, const bf16* __restrict__ W, const void* __restrict__ bias,
+    int bias_bf16, const bf16* __restrict__ res, bf16* __restrict__ Y, bf16* __restrict__ Z,
     int M, int N, int K) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   short* xs = reinterpret_cast<short*>(smem);              // [2][BM][PITCH]
@@ -212,6 +218,14 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(
     __syncthreads();
   }
 
+  float bv[4] = {};
+  if (HAS_BIAS) {
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      const int n = n0 + wn + 16 * ni + lo;
+      if (n < N) bv[ni] = load_bias(bias, n, bias_bf16);
+    }
+  }
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
@@ -222,7 +236,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(
       for (int ni = 0; ni < 4; ++ni) {
         const int n = n0 + wn + 16 * ni + lo;
         if (n >= N) continue;
-        gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE_PRE>(acc[mi][ni][r], m, n, N, bias, res, Y, Z);
+        gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE>(acc[mi][ni][r], m, n, N, bv[ni], res, Y, Z);
       }
     }
   }
@@ -232,9 +246,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(
 
 // 8-phase 256x256-tile kernel (gemm8p.hip)
 bool gemm8p_supported(int64_t M, int64_t N, int64_t K);
-void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias_f32,
+void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias,
                 std::string act, c10::optional<torch::Tensor> residual, torch::Tensor y,
-                c10::optional<torch::Tensor> z);
+                int save, c10::optional<torch::Tensor> z);
 
 bool gemm_supported(int64_t M, int64_t N, int64_t K, std::string dtype) {
   if (dtype != "torch.bfloat16") return false;
@@ -244,53 +258,94 @@ bool gemm_supported(int64_t M, int64_t N, int64_t K, std::string dtype) {
   return true;
 }
 
-std::vector<torch::Tensor> linear_fwd(torch::Tensor x, torch::Tensor w,
-                                      c10::optional<torch::Tensor> bias, std::string act,
-                                      c10::optional<torch::Tensor> residual, bool save_z) {
+namespace {
+
+// y = act(x @ w^T + bias) [+ residual] and, per `save` (SAVE_*), nothing,
+// the bf16 pre-activation or the fp16 activation derivative as the second
+// tensor (undefined = None in Python for SAVE_NONE).
+std::vector<torch::Tensor> linear_fwd_impl(torch::Tensor x, torch::Tensor w,
+                                           c10::optional<torch::Tensor> bias, std::string act,
+                                           c10::optional<torch::Tensor> residual, int save) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && w.is_contiguous());
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2);
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K && K % BK == 0);
+  TORCH_CHECK(save != SAVE_GRAD || !act.empty(),
+              "saving the activation derivative needs an activation");
+  if (residual)
+    TORCH_CHECK(residual->is_contiguous() && residual->scalar_type() == torch::kBFloat16 &&
+                residual->numel() == (int64_t)M * N);
   auto y = torch::empty({M, N}, x.options());
-  torch::Tensor z;  // stays undefined (None in Python) unless save_z
-  if (save_z) z = torch::empty({M, N}, x.options());
-  c10::optional<torch::Tensor> bf;
-  if (bias) bf = bias->contiguous().to(torch::kFloat32);
+  torch::Tensor z;
+  if (save == SAVE_PRE) z = torch::empty({M, N}, x.options());
+  if (save == SAVE_GRAD) z = torch::empty({M, N}, x.options().dtype(torch::kFloat16));
+  // The kernels read an fp32 or a bf16 bias as it is (no cast kernel per
+  // call); any other dtype goes through fp32.
+  c10::optional<torch::Tensor> b;
+  if (bias) {
+    TORCH_CHECK(bias->numel() == N);
+    b = bias->contiguous();
+    if (b->scalar_type() != torch::kBFloat16 && b->scalar_type() != torch::kFloat32)
+      b = b->to(torch::kFloat32);
+  }
+  c10::optional<torch::Tensor> zopt;
+  if (save != SAVE_NONE) zopt = z;
 
   if (gemm8p_supported(M, N, K)) {
-    c10::optional<torch::Tensor> zopt;
-    if (save_z) zopt = z;
-    gemm_nt_8p(x, w, bf, act, residual, y, zopt);
+    gemm_nt_8p(x, w, b, act, residual, y, save, zopt);
     return {y, z};
   }
 
   auto stream = at::hip::getCurrentHIPStream();
   const bf16* xp = reinterpret_cast<const bf16*>(x.data_ptr());
   const bf16* wp = reinterpret_cast<const bf16*>(w.data_ptr());
-  const float* biasp = bf ? bf->data_ptr<float>() : nullptr;
+  const void* biasp = b ? b->data_ptr() : nullptr;
+  const int bias_bf16 = b && b->scalar_type() == torch::kBFloat16;
   const bf16* resp = residual ? reinterpret_cast<const bf16*>(residual->data_ptr()) : nullptr;
   bf16* yp = reinterpret_cast<bf16*>(y.data_ptr());
-  bf16* zp = save_z ? reinterpret_cast<bf16*>(z.data_ptr()) : nullptr;
+  bf16* zp = zopt ? reinterpret_cast<bf16*>(z.data_ptr()) : nullptr;
   const bool fast = (M % BM == 0) && (N % BN == 0);
   with_act(act_code(act), [&](auto act_c) {
-    with_flags(
-        [&](auto hb, auto hr, auto sp, auto fast_c) {
-          constexpr int A = decltype(act_c)::value;
-          constexpr bool HB = decltype(hb)::value, HR = decltype(hr)::value,
-                         SP = decltype(sp)::value;
-          if constexpr (decltype(fast_c)::value) {
-            constexpr size_t shmem = 4 * 8192 * sizeof(short);
-            launch_lds<gemm_nt_fast_kernel<A, HB, HR, SP>>(dim3((M / BM) * (N / BN)), dim3(256),
-                                                           shmem, shmem, stream, xp, wp, biasp,
-                                                           resp, yp, zp, M, N, K);
-          } else {
-            constexpr size_t shmem = 2 * (BM + BN) * PITCH * sizeof(short);
-            launch_lds<gemm_nt_kernel<A, HB, HR, SP>>(
-                dim3((M + BM - 1) / BM, (N + BN - 1) / BN), dim3(256), shmem, shmem, stream, xp,
-                wp, biasp, resp, yp, zp, M, N, K);
-          }
-        },
-        bias.has_value(), residual.has_value(), save_z, fast);
+    with_save(save, [&](auto save_c) {
+      with_flags(
+          [&](auto hb, auto hr, auto fast_c) {
+            constexpr int A = decltype(act_c)::value, S = decltype(save_c)::value;
+            constexpr bool HB = decltype(hb)::value, HR = decltype(hr)::value;
+            if constexpr (S == SAVE_GRAD && A == ACT_NONE) {
+              TORCH_CHECK(false, "saving the activation derivative needs an activation");
+            } else if constexpr (decltype(fast_c)::value) {
+              constexpr size_t shmem = 4 * 8192 * sizeof(short);
+              launch_lds<gemm_nt_fast_kernel<A, HB, HR, S>>(
+                  dim3((M / BM) * (N / BN)), dim3(256), shmem, shmem, stream, xp, wp, biasp,
+                  bias_bf16, resp, yp, zp, M, N, K);
+            } else {
+              constexpr size_t shmem = 2 * (BM + BN) * PITCH * sizeof(short);
+              launch_lds<gemm_nt_kernel<A, HB, HR, S>>(
+                  dim3((M + BM - 1) / BM, (N + BN - 1) / BN), dim3(256), shmem, shmem, stream,
+                  xp, wp, biasp, bias_bf16, resp, yp, zp, M, N, K);
+            }
+          },
+          bias.has_value(), residual.has_value(), fast);
+    });
   });
   return {y, z};
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> linear_fwd(torch::Tensor x, torch::Tensor w,
+                                      c10::optional<torch::Tensor> bias, std::string act,
+                                      c10::optional<torch::Tensor> residual, bool save_z) {
+  return linear_fwd_impl(x, w, bias, act, residual, save_z ? SAVE_PRE : SAVE_NONE);
+}
+
+// The forward of an activated linear that saves g = act'(x @ w^T + bias) as
+// fp16 in place of the pre-activation: returns {y, g}, y bitwise what
+// linear_fwd returns. gemm_nt_8p_gradmul consumes g.
+std::vector<torch::Tensor> linear_fwd_actgrad(torch::Tensor x, torch::Tensor w,
+                                              c10::optional<torch::Tensor> bias,
+                                              std::string act,
+                                              c10::optional<torch::Tensor> residual) {
+  return linear_fwd_impl(x, w, bias, act, residual, SAVE_GRAD);
 }

@@ -40,7 +40,12 @@
 // row-XOR spreads them over all 16 slots).  glds writes lane-linear; the
 // inverse permutation goes on the per-lane SOURCE address (§5.4 rule 21).
 //
-// Epilogue fuses bias + gelu/gelu_tanh/quickgelu (+residual, +save-pre).
+// Epilogue fuses bias (fp32 or bf16, a lane's 4 values loaded once) +
+// gelu/gelu_tanh/quickgelu (+residual) and saves nothing, the bf16
+// pre-activation or the fp16 activation derivative (SAVE_*, mfma.h); the dX
+// variants multiply by act'(z) recomputed from a saved z (GRADM_ACT) or by a
+// saved fp16 derivative (GRADM_MUL: one load, convert and multiply per
+// element, no activation code).
 // M may be ragged (MGUARD clamps staging rows and predicates stores);
 // N%256==0, K%64==0, K>=128 required (gemm8p_supported).
 
@@ -83,11 +88,11 @@ __device__ __forceinline__ int frag_off(int row, int chunk) {
   return (row << 7) + ((chunk ^ (row & 7)) << 4);
 }
 
-template <int ACT, bool HAS_BIAS, bool HAS_RES, bool SAVE_PRE, bool MGUARD, bool GRADM = false,
+template <int ACT, bool HAS_BIAS, bool HAS_RES, int SAVE, bool MGUARD, int GRADM = GRADM_NONE,
           bool FP8O = false>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
-    const bf16* __restrict__ X, const bf16* __restrict__ W, const float* __restrict__ bias,
-    const bf16* __restrict__ res, bf16* __restrict__ Y, bf16* __restrict__ Z,
+    const bf16* __restrict__ X, const bf16* __restrict__ W, const void* __restrict__ bias,
+    int bias_bf16, const bf16* __restrict__ res, bf16* __restrict__ Y, bf16* __restrict__ Z,
     int M, int N, int K, unsigned char* __restrict__ Y8 = nullptr,
     const float* __restrict__ scale8 = nullptr,
     unsigned int* __restrict__ amax_bits = nullptr) {
@@ -219,7 +224,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
   // Epilogue: acc[pr][mi][ni] -> rows m0 + pr*128 + wm*64 + 16mi + hi*4 + r,
   // cols n0 + wn*64 + 16ni + lo.
   float rs8 = 1.f, tmax = 0.f;
-  if (FP8O) rs8 = 1.f / scale8[0];
+  if (FP8O) rs8 = fast_rcpf(scale8[0]);
+  // a lane owns 4 columns (n depends on ni alone): its bias values, once
+  float bv[4] = {};
+  if (HAS_BIAS) {
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+      bv[ni] = load_bias(bias, n0 + wn * 64 + 16 * ni + lo, bias_bf16);
+  }
 #pragma unroll
   for (int pr = 0; pr < 2; ++pr) {
 #pragma unroll
@@ -231,8 +243,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           const int n = n0 + wn * 64 + 16 * ni + lo;
-          gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE_PRE, GRADM, FP8O>(
-              acc[pr][mi][ni][r], m, n, N, bias, res, Y, Z, Y8, rs8, &tmax);
+          gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE, GRADM, FP8O>(
+              acc[pr][mi][ni][r], m, n, N, bv[ni], res, Y, Z, Y8, rs8, &tmax);
         }
       }
     }
@@ -254,7 +266,7 @@ namespace {
 // One launch of a gemm_nt_8p_kernel instantiation: 160 KiB of LDS (the full
 // CU), one workgroup per 256x256 output tile.
 template <auto Kernel>
-void launch_8p(const torch::Tensor& x, const torch::Tensor& w, const float* biasp,
+void launch_8p(const torch::Tensor& x, const torch::Tensor& w, const void* biasp, int bias_bf16,
                const bf16* resp, torch::Tensor& y, bf16* zp, unsigned char* y8p = nullptr,
                const float* scale8p = nullptr, unsigned int* amaxp = nullptr) {
   const int M = x.size(0), K = x.size(1), N = w.size(0);
@@ -262,7 +274,7 @@ void launch_8p(const torch::Tensor& x, const torch::Tensor& w, const float* bias
   const int mt = (M + BM - 1) / BM;
   launch_lds<Kernel>(dim3(mt * (N / BN)), dim3(NTHREADS), shmem, shmem,
                      at::hip::getCurrentHIPStream(), reinterpret_cast<const bf16*>(x.data_ptr()),
-                     reinterpret_cast<const bf16*>(w.data_ptr()), biasp, resp,
+                     reinterpret_cast<const bf16*>(w.data_ptr()), biasp, bias_bf16, resp,
                      reinterpret_cast<bf16*>(y.data_ptr()), zp, M, N, K, y8p, scale8p, amaxp);
 }
 
@@ -293,9 +305,9 @@ std::vector<torch::Tensor> gradact_8p(torch::Tensor dy, torch::Tensor wt, torch:
         [&](auto mg, auto fp8_c) {
           constexpr int A = decltype(act_c)::value;
           if constexpr (A != ACT_NONE)
-            launch_8p<gemm_nt_8p_kernel<A, false, true, false, decltype(mg)::value, true,
-                                        decltype(fp8_c)::value>>(dy, wt, nullptr, zp, y, nullptr,
-                                                                 y8p, scale8p, amaxp);
+            launch_8p<gemm_nt_8p_kernel<A, false, true, SAVE_NONE, decltype(mg)::value, GRADM_ACT,
+                                        decltype(fp8_c)::value>>(dy, wt, nullptr, 0, zp, y,
+                                                                 nullptr, y8p, scale8p, amaxp);
         },
         (M % BM) != 0, fp8);
   });
@@ -316,21 +328,54 @@ std::vector<torch::Tensor> gemm_nt_8p_gradact_fp8(torch::Tensor dy, torch::Tenso
   return gradact_8p(dy, wt, z, act, scale8, amax);
 }
 
-void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias_f32,
+// dz = (dy @ wt^T) * g with g the fp16 activation derivative a SAVE_GRAD
+// forward stored: the gradact GEMM with the multiplier read instead of
+// computed (no activation code in the epilogue).
+torch::Tensor gemm_nt_8p_gradmul(torch::Tensor dy, torch::Tensor wt, torch::Tensor g) {
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && wt.is_contiguous() && g.is_contiguous());
+  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 && wt.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(g.scalar_type() == torch::kFloat16, "gradmul needs an fp16 multiplier");
+  TORCH_CHECK(dy.dim() == 2 && wt.dim() == 2 && g.dim() == 2);
+  const int M = dy.size(0), K = dy.size(1), N = wt.size(0);
+  TORCH_CHECK(wt.size(1) == K && g.size(0) == M && g.size(1) == N);
+  TORCH_CHECK(gemm8p_supported(M, N, K));
+  auto y = torch::empty({M, N}, dy.options());
+  const bf16* gp = reinterpret_cast<const bf16*>(g.data_ptr());
+  with_flags(
+      [&](auto mg) {
+        launch_8p<gemm_nt_8p_kernel<ACT_NONE, false, true, SAVE_NONE, decltype(mg)::value,
+                                    GRADM_MUL>>(dy, wt, nullptr, 0, gp, y, nullptr);
+      },
+      (M % BM) != 0);
+  return y;
+}
+
+// bias: fp32 or bf16, read as it is. save: SAVE_*; z receives what it names.
+void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias,
                 std::string act, c10::optional<torch::Tensor> residual, torch::Tensor y,
-                c10::optional<torch::Tensor> z) {
+                int save, c10::optional<torch::Tensor> z) {
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(gemm8p_supported(M, N, K));
+  TORCH_CHECK((save != SAVE_NONE) == z.has_value());
   const bf16* resp = residual ? reinterpret_cast<const bf16*>(residual->data_ptr()) : nullptr;
-  const float* biasp = bias_f32 ? bias_f32->data_ptr<float>() : nullptr;
+  const void* biasp = bias ? bias->data_ptr() : nullptr;
+  const int bias_bf16 = bias && bias->scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(!bias || bias_bf16 || bias->scalar_type() == torch::kFloat32);
   bf16* zp = z ? reinterpret_cast<bf16*>(z->data_ptr()) : nullptr;
   with_act(act_code(act), [&](auto act_c) {
-    with_flags(
-        [&](auto hb, auto hr, auto sp, auto mg) {
-          launch_8p<gemm_nt_8p_kernel<decltype(act_c)::value, decltype(hb)::value,
-                                      decltype(hr)::value, decltype(sp)::value,
-                                      decltype(mg)::value>>(x, w, biasp, resp, y, zp);
-        },
-        bias_f32.has_value(), residual.has_value(), z.has_value(), (M % BM) != 0);
+    with_save(save, [&](auto save_c) {
+      with_flags(
+          [&](auto hb, auto hr, auto mg) {
+            constexpr int A = decltype(act_c)::value, S = decltype(save_c)::value;
+            if constexpr (S == SAVE_GRAD && A == ACT_NONE) {
+              TORCH_CHECK(false, "saving the activation derivative needs an activation");
+            } else {
+              launch_8p<gemm_nt_8p_kernel<A, decltype(hb)::value, decltype(hr)::value, S,
+                                          decltype(mg)::value>>(x, w, biasp, bias_bf16, resp, y,
+                                                                zp);
+            }
+          },
+          bias.has_value(), residual.has_value(), (M % BM) != 0);
+    });
   });
 }

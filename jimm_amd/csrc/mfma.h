@@ -108,27 +108,60 @@ __device__ __forceinline__ void tr_frag_x2(lds_cp base, bf16x8 (&out)[2]) {
 
 // ---- fused GEMM epilogue ---------------------------------------------------
 
+// What a forward GEMM writes to Z beside Y: nothing, the pre-activation
+// (bf16), or the activation derivative act'(vpre) as fp16 (activated GEMMs
+// only). The derivative lies in about [-0.17, 1.13], so fp16's 11 bits cost
+// no range, and the backward is left with one multiply (GRADM_MUL).
+#define SAVE_NONE 0
+#define SAVE_PRE 1
+#define SAVE_GRAD 2
+
+// dX GEMM of an activated linear with the activation backward fused in:
+// GRADM_ACT recomputes act'(z) from the saved bf16 pre-activation,
+// GRADM_MUL reads the saved fp16 derivative. res carries either.
+#define GRADM_NONE 0
+#define GRADM_ACT 1
+#define GRADM_MUL 2
+
+// bias[n] as fp32 from an fp32 or a bf16 bias vector (wave-uniform flag; a
+// lane needs only the few columns it owns, so callers load these once per
+// tile, outside the element loops).
+__device__ __forceinline__ float load_bias(const void* bias, int n, int bias_bf16) {
+  return bias_bf16 ? bf2f(static_cast<const bf16*>(bias)[n])
+                   : static_cast<const float*>(bias)[n];
+}
+
 // One accumulator value of an NT GEMM at (m, n), already inside the bounds:
-//   vpre = acc (+ bias[n]);  Z = vpre (SAVE_PRE);
+//   vpre = acc (+ bias_n);  Z = vpre (SAVE_PRE) or fp16 act'(vpre) (SAVE_GRAD)
 //   Y = act(vpre) (+ res)                      forward
-//   Y = vpre * act'(res)                       GRADM: the dX GEMM of an
-//       activated linear with the activation backward fused in; res carries
-//       the saved pre-activation z
+//   Y = vpre * act'(res)                       GRADM_ACT
+//   Y = vpre * res (fp16)                      GRADM_MUL
 //   Y8 = e4m3(Y * rs8), *tmax = max(*tmax, |Y|)   FP8O: delayed-scaled e4m3
 //       copy (consumed by the fp8 dX GEMM); the caller reduces tmax.
-template <int ACT, bool HAS_BIAS, bool HAS_RES, bool SAVE_PRE, bool GRADM = false,
+// Y is the same bits in every SAVE mode: act_fwd is act_fwd_grad with the
+// derivative dropped.
+template <int ACT, bool HAS_BIAS, bool HAS_RES, int SAVE, int GRADM = GRADM_NONE,
           bool FP8O = false>
-__device__ __forceinline__ void gemm_epilogue(float vpre, int m, int n, int N, const float* bias,
+__device__ __forceinline__ void gemm_epilogue(float vpre, int m, int n, int N, float bias_n,
                                               const bf16* res, bf16* Y, bf16* Z,
                                               unsigned char* Y8 = nullptr, float rs8 = 1.f,
                                               float* tmax = nullptr) {
-  if (HAS_BIAS) vpre += bias[n];
-  if (SAVE_PRE) Z[(int64_t)m * N + n] = f2bf(vpre);
+  static_assert(SAVE != SAVE_GRAD || ACT != ACT_NONE, "SAVE_GRAD needs an activation");
+  if (HAS_BIAS) vpre += bias_n;
+  if (SAVE == SAVE_PRE) Z[(int64_t)m * N + n] = f2bf(vpre);
   float vy;
-  if (GRADM) {
+  if (GRADM == GRADM_ACT) {
     vy = vpre * act_grad(bf2f(res[(int64_t)m * N + n]), ACT);
+  } else if (GRADM == GRADM_MUL) {
+    vy = vpre * __half2float(reinterpret_cast<const __half*>(res)[(int64_t)m * N + n]);
   } else {
-    vy = act_fwd(vpre, ACT);
+    if (SAVE == SAVE_GRAD) {
+      float g;
+      vy = act_fwd_grad(vpre, ACT, &g);
+      reinterpret_cast<__half*>(Z)[(int64_t)m * N + n] = __float2half(g);
+    } else {
+      vy = act_fwd(vpre, ACT);
+    }
     if (HAS_RES) vy += bf2f(res[(int64_t)m * N + n]);
   }
   Y[(int64_t)m * N + n] = f2bf(vy);
@@ -145,7 +178,7 @@ __device__ __forceinline__ void gemm_epilogue(float vpre, int m, int n, int N, c
 int act_code(const std::string& act);
 
 // Run-time values -> template arguments. with_act calls f with a
-// std::integral_constant<int, ACT_*>; with_flags calls f with one
+// std::integral_constant<int, ACT_*> (with_save likewise); with_flags calls f with one
 // std::true_type / std::false_type per bool, in order. Read them back with
 // decltype(c)::value.
 template <typename F>
@@ -157,6 +190,17 @@ void with_act(int act, F&& f) {
     case ACT_QUICKGELU: return f(std::integral_constant<int, ACT_QUICKGELU>{});
   }
   TORCH_CHECK(false, "bad activation code ", act);
+}
+
+// with_save calls f with a std::integral_constant<int, SAVE_*>.
+template <typename F>
+void with_save(int save, F&& f) {
+  switch (save) {
+    case SAVE_NONE: return f(std::integral_constant<int, SAVE_NONE>{});
+    case SAVE_PRE: return f(std::integral_constant<int, SAVE_PRE>{});
+    case SAVE_GRAD: return f(std::integral_constant<int, SAVE_GRAD>{});
+  }
+  TORCH_CHECK(false, "bad save mode ", save);
 }
 
 template <typename F>

@@ -31,6 +31,15 @@ def _hip_gemms(M: int, H: int) -> bool:
     return _gemm_mode() == "hip" and H % 256 == 0
 
 
+def _act_save_g() -> bool:
+    """What the bf16 HIP path keeps of fc1 for the backward: the fp16
+    activation derivative g = act'(z1), computed by the forward epilogue from
+    values it already holds, so that fc2-dX is left with one multiply
+    (default), or, with JIMM_AMD_ACT_SAVE=z, the bf16 pre-activation z1,
+    from which the fc2-dX epilogue recomputes the derivative (A/B)."""
+    return os.environ.get("JIMM_AMD_ACT_SAVE", "g") != "z"
+
+
 # minimum rows x hidden for the fp8 block path (tests lower it to force fp8)
 _FP8_MIN_MH = 1 << 26
 
@@ -158,7 +167,14 @@ class EncoderBlockFn(torch.autograd.Function):
             a, _ = ext.linear_fwd(o2, wproj, bproj, "", x2, False)
             a3 = a.view(B, L, H)
             h2, mean2, rstd2 = ext.layernorm_fwd(a3, ln2w, ln2b, eps)
-            f, z1 = ext.linear_fwd(h2.view(-1, H), w1, b1, act, None, True)
+            # fc2-dX runs as (M, mlp, H); where the 8-phase kernel takes it,
+            # z1 holds the fp16 derivative act'(pre) instead of the
+            # pre-activation (nothing else reads z1)
+            save_g = _act_save_g() and ext.gemm8p_supported(B * L, w1.shape[0], H)
+            if save_g:
+                f, z1 = ext.linear_fwd_actgrad(h2.view(-1, H), w1, b1, act, None)
+            else:
+                f, z1 = ext.linear_fwd(h2.view(-1, H), w1, b1, act, None, True)
             y, _ = ext.linear_fwd(f, w2, b2, "", a, False)
         else:
             a2 = torch.matmul(o2, wproj.t())
@@ -198,6 +214,9 @@ class EncoderBlockFn(torch.autograd.Function):
             dz1, dz18 = ext.gemm_nt_8p_gradact_fp8(
                 dy2, w2.t().contiguous(), z1, act, scale8[3:4], amax8[3:4]
             )
+        elif hip and z1.dtype == torch.float16:
+            # the forward saved g = act'(pre): dz1 = (dy @ W2) * g
+            dz1 = ext.gemm_nt_8p_gradmul(dy2, w2.t().contiguous(), z1)
         elif hip:
             # dX of fc2 with the activation backward fused into the GEMM
             # epilogue: dz1 = (dy @ W2) * act'(z1) — no separate act_bwd pass
