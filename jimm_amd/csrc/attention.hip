@@ -5,12 +5,13 @@
 // heads = width/64 — clip.py:60), causal masking for the CLIP text tower
 // (clip.py:62), and the MAP head's Lq=1 cross-attention (K9).
 //
-// Design (one workgroup = 4 waves = 64 q rows; grid = (ceil(Lq/64), B*H)):
+// Design (one workgroup = 4 waves = NSTRIP strips of 64 q rows, 16 rows per
+// wave and strip; grid = (ceil(ceil(Lq/64)/NSTRIP), B*H)):
 //   * "swapped" QK^T: S^T = mfma(A=K_tile, B=Q^T) so each lane's softmax
 //     row stats live in-lane + 2 shuffles (no serial-lane softmax — CDNA
 //     guide common-mistake #6);
-//   * K staged row-major in LDS, V staged TRANSPOSED (V^T) so the PV
-//     mfma's B-fragment is a contiguous ds_read_b128;
+//   * K staged row-major in LDS, V staged as a block image whose transposed
+//     reads (ds_read_b64_tr_b16) deliver the PV mfma's B-fragments;
 //   * P routed through a per-wave LDS tile (padded rows, +8 shorts) to
 //     re-shape from the S^T C-layout into the PV A-fragment layout;
 //   * online softmax with running (m, l) per q row; lse = m + log(l)
@@ -29,13 +30,11 @@
 
 namespace {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int QBLK = 64;    // q rows per strip (16 per wave)
-// NSTRIP (q strips per workgroup) is a template param: 4 = fewer K/V
-// staging passes, 2 waves/SIMD; 2 = 3 waves/SIMD, twice the staging
-// (JIMM_AMD_ATTN_NSTRIP selects; default 4)
+// q strips per workgroup: 2 keeps 3 waves/SIMD at every head dim and staging
+// length (4 strips halve the K/V staging passes but drop to 2 waves/SIMD and
+// measured slower everywhere: L=257 207 -> 168 TF/s)
+constexpr int NSTRIP = 2;
 constexpr int KVBLK = 64;   // keys per LDS tile
 
 // Head dims beyond 64: the kernel is templated on the
@@ -43,24 +42,22 @@ constexpr int KVBLK = 64;   // keys per LDS tile
 //
 // V block image (boff<DP>, mfma.h): [64 key][DP d], written with vector
 // ds_write_b128 from the row-major staging registers and read as PV
-// B-fragments with tr_frag_x4 / tr_frag_x2 at per-lane address
-// base + lane*8 B.
+// B-fragments with tr_frags at per-lane address base + lane*8 B.
 
-template <bool CAUSAL, int NSTRIP, int DP>
+template <bool CAUSAL, int DP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     bf16* __restrict__ o, float* __restrict__ lse, int Lq, int Lk, float scale, int H, int Dr,
-    int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-    int64_t v_sb, int64_t v_sh, int64_t v_sl, int64_t o_sb, int64_t o_sh, int64_t o_sl) {
-  // (sb, sh, sl) = element strides of the (B,H,L,64) view; innermost dim is
-  // contiguous. Covers contiguous BHLD, (B,L,H,64) and fused-qkv (B,L,3,H,64)
+    hstride q_s, hstride k_s, hstride v_s, hstride o_s) {
+  // Strides are those of the (B,H,L,D) views; the innermost dim is
+  // contiguous. Covers contiguous BHLD, (B,L,H,D) and fused-qkv (B,L,3,H,D)
   // layouts with no permute copies.
   //
   // Each workgroup covers up to NSTRIP x 64 q rows of one (b,h): K/V tiles
-  // are staged ONCE per kv tile for all strips (the 1-strip version staged
-  // them once per 64-q workgroup — 4x redundant global traffic at L=197,
-  // ~125 of its 213 us bandwidth-bound). T14 split staging + single LDS
-  // buffer; each wave keeps NSTRIP online-softmax states.
+  // are staged ONCE per kv tile for all strips (one strip per workgroup is
+  // 4x redundant global traffic at L=197, ~125 of its 213 us
+  // bandwidth-bound). T14 split staging; each wave keeps NSTRIP
+  // online-softmax states.
   constexpr int LDS_PITCH = DP + 8;  // bank-conflict pad for b128 reads
   constexpr int NS = DP / 32;        // d-steps per fragment contraction
   constexpr int NT = DP / 16;        // d-tiles of the output
@@ -78,21 +75,20 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
   const int lo = lane & 15;   // column index inside a 16-wide fragment
   const int hi = lane >> 4;   // 0..3
   const int64_t bh = blockIdx.y;
-  const int64_t b = bh / H, h = bh % H;
   // cyclic strip -> q-tile mapping: strip t covers q tile
   // (blockIdx.x + t*gridDim.x) — balances ragged L (a blocked mapping gives
   // the last workgroup a nearly-empty supertile, e.g. 1 of 256 rows at L=257)
   const int ntq = (Lq + QBLK - 1) / QBLK;
 
-  const bf16* qp = q + b * q_sb + h * q_sh;
-  const bf16* kp = k + b * k_sb + h * k_sh;
-  const bf16* vp = v + b * v_sb + h * v_sh;
-  bf16* op = o + b * o_sb + h * o_sh;
+  const bf16* qp = head_ptr(q, q_s, bh, H);
+  const bf16* kp = head_ptr(k, k_s, bh, H);
+  const bf16* vp = head_ptr(v, v_s, bh, H);
+  bf16* op = head_ptr(o, o_s, bh, H);
 
   // ---- load Q fragments for every strip (B-operand of the swapped QK^T) --
   // strip t covers q rows [q_base + t*64, +64); this wave's rows:
   // q0(t) = q_base + t*64 + wave*16; B[d][q] = Q[q0+lo][32*s + hi*8 + j]
-  bf16x8_t qb[NSTRIP][NS];
+  bf16x8 qb[NSTRIP][NS];
   int nactive = 0;
 #pragma unroll
   for (int t = 0; t < NSTRIP; ++t) {
@@ -101,12 +97,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const int qrow = min(min(ti, ntq - 1) * QBLK + wave * 16 + lo, Lq - 1);
 #pragma unroll
     for (int s = 0; s < NS; ++s)
-      qb[t][s] = ld8g<DP>(qp + (int64_t)qrow * q_sl, 32 * s + hi * 8, Dr);
+      qb[t][s] = ld8g<DP>(qp + (int64_t)qrow * q_s.l, 32 * s + hi * 8, Dr);
   }
 
   short* my_p = p_lds + wave * 16 * LDS_PITCH;
 
-  f32x4_t acc_o[NSTRIP][NT] = {};  // O tiles: rows q = hi*4+r, cols d = 16*dt+lo
+  f32x4 acc_o[NSTRIP][NT] = {};  // O tiles: rows q = hi*4+r, cols d = 16*dt+lo
   float m_run[NSTRIP], l_run[NSTRIP];
 #pragma unroll
   for (int t = 0; t < NSTRIP; ++t) {
@@ -121,7 +117,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
   constexpr int NCG = (DP + 63) / 64;  // 64-wide column groups per row
   const int st_row = tid / 4;
   const int st_c0 = (tid % 4) * 16;
-  bf16x8_t kreg[NCG][2], vreg[NCG][2];
+  bf16x8 kreg[NCG][2], vreg[NCG][2];
   bool st_valid;
   auto load_tile_regs = [&](int kv0) {
     const int key = kv0 + st_row;
@@ -131,10 +127,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     for (int cg = 0; cg < NCG; ++cg) {
       const int c0 = cg * 64 + st_c0;
       if (c0 >= DP) continue;
-      kreg[cg][0] = ld8g<DP>(kp + (int64_t)krow * k_sl, c0, Dr);
-      kreg[cg][1] = ld8g<DP>(kp + (int64_t)krow * k_sl, c0 + 8, Dr);
-      vreg[cg][0] = ld8g<DP>(vp + (int64_t)krow * v_sl, c0, Dr);
-      vreg[cg][1] = ld8g<DP>(vp + (int64_t)krow * v_sl, c0 + 8, Dr);
+      kreg[cg][0] = ld8g<DP>(kp + (int64_t)krow * k_s.l, c0, Dr);
+      kreg[cg][1] = ld8g<DP>(kp + (int64_t)krow * k_s.l, c0 + 8, Dr);
+      vreg[cg][0] = ld8g<DP>(vp + (int64_t)krow * v_s.l, c0, Dr);
+      vreg[cg][1] = ld8g<DP>(vp + (int64_t)krow * v_s.l, c0 + 8, Dr);
     }
   };
   auto write_tile = [&](int buf) {
@@ -143,14 +139,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     for (int cg = 0; cg < NCG; ++cg) {
       const int c0 = cg * 64 + st_c0;
       if (c0 >= DP) continue;
-      const bf16x8_t k0 = st_valid ? kreg[cg][0] : bf16x8_t{};
-      const bf16x8_t k1 = st_valid ? kreg[cg][1] : bf16x8_t{};
-      const bf16x8_t v0 = st_valid ? vreg[cg][0] : bf16x8_t{};
-      const bf16x8_t v1 = st_valid ? vreg[cg][1] : bf16x8_t{};
-      *reinterpret_cast<bf16x8_t*>(k_lds + bo + st_row * LDS_PITCH + c0) = k0;
-      *reinterpret_cast<bf16x8_t*>(k_lds + bo + st_row * LDS_PITCH + c0 + 8) = k1;
-      *reinterpret_cast<bf16x8_t*>(vt_lds + bo + boff<DP>(st_row, c0)) = v0;
-      *reinterpret_cast<bf16x8_t*>(vt_lds + bo + boff<DP>(st_row, c0 + 8)) = v1;
+      const bf16x8 k0 = st_valid ? kreg[cg][0] : bf16x8{};
+      const bf16x8 k1 = st_valid ? kreg[cg][1] : bf16x8{};
+      const bf16x8 v0 = st_valid ? vreg[cg][0] : bf16x8{};
+      const bf16x8 v1 = st_valid ? vreg[cg][1] : bf16x8{};
+      *reinterpret_cast<bf16x8*>(k_lds + bo + st_row * LDS_PITCH + c0) = k0;
+      *reinterpret_cast<bf16x8*>(k_lds + bo + st_row * LDS_PITCH + c0 + 8) = k1;
+      *reinterpret_cast<bf16x8*>(vt_lds + bo + boff<DP>(st_row, c0)) = v0;
+      *reinterpret_cast<bf16x8*>(vt_lds + bo + boff<DP>(st_row, c0 + 8)) = v1;
     }
   };
 
@@ -180,14 +176,13 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
       const int kv_hi = CAUSAL ? min(Lk, q0 + 16) : Lk;
       // ---- S^T = K . Q^T : 4 key tiles x NS d-steps -----------------------
       __builtin_amdgcn_s_setprio(1);
-      f32x4_t sc[4] = {};
+      f32x4 sc[4] = {};
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         if (kv0 + 16 * t >= kv_hi) continue;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          const bf16x8_t ka =
-              *reinterpret_cast<const bf16x8_t*>(k_lds + sbo + (16 * t + lo) * LDS_PITCH + 32 * s + hi * 8);
+          const bf16x8 ka = row_frag(k_lds + sbo, 16 * t + lo, LDS_PITCH, s, hi);
           sc[t] = MFMA16(ka, qb[st][s], sc[t]);
         }
       }
@@ -250,13 +245,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if (kv0 + 32 * s >= kv_hi) continue;  // P = 0 for the whole step
-        bf16x8_t vb[NT];
-        const lds_cp bbase = (lds_cp)(const void*)(vt_lds + sbo + s * 32 * DP) + lane * 8;
-        tr_frag_x4(bbase, *reinterpret_cast<bf16x8_t(*)[4]>(&vb[0]));
-        if constexpr (NT == 6) tr_frag_x2(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[2]>(&vb[4]));
-        if constexpr (NT == 8) tr_frag_x4(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[4]>(&vb[4]));
-        const bf16x8_t pa =
-            *reinterpret_cast<const bf16x8_t*>(my_p + lo * LDS_PITCH + 32 * s + hi * 8);
+        bf16x8 vb[NT];
+        tr_frags<NT>((lds_cp)(const void*)(vt_lds + sbo + s * 32 * DP) + lane * 8, vb);
+        const bf16x8 pa = row_frag(my_p, lo, LDS_PITCH, s, hi);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int dt = 0; dt < NT; ++dt) acc_o[st][dt] = MFMA16(pa, vb[dt], acc_o[st][dt]);
@@ -284,7 +275,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
 #pragma unroll
       for (int dt = 0; dt < NT; ++dt)
         if (DP == 64 || 16 * dt + lo < Dr)
-          op[(int64_t)qrow * o_sl + 16 * dt + lo] = f2bf(acc_o[st][dt][r] * invl_r[r]);
+          op[(int64_t)qrow * o_s.l + 16 * dt + lo] = f2bf(acc_o[st][dt][r] * invl_r[r]);
     }
     if (hi == 0 && q0 + lo < Lq)
       lse[bh * Lq + q0 + lo] = m_run[st] + __logf(l_run[st]);
@@ -295,14 +286,17 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
 // Small-L fast path (VERDICT r01 #4 — CLIP text L=77 causal was the worst
 // kernel in the zoo): at L <= 80 the general kernel is OVERHEAD-bound —
 // its 4-wave workgroups spend most of their time in barriers/staging for a
-// few nearly-empty tiles. Here one WAVE owns one whole (b,h) attention:
-//   * grid = ceil(B*H/4), 4 independent waves per workgroup, ZERO barriers
-//     (each wave reads only its own LDS slice; its own ds writes are
-//     ordered by the compiler's lgkmcnt / the tr-asm's lgkmcnt(0));
-//   * K and V staged once per wave into BLOCK images (row-fragment reads
-//     for QK^T, tr_b16 reads for PV);
+// few nearly-empty tiles. Here one 5-wave workgroup owns one whole (b,h):
+//   * grid = B*H; wave w owns the 16-query strip w (<= 5 strips at L <= 80);
+//   * V staged once into a shared BLOCK image (tr_b16 reads for PV), ONE
+//     barrier; K lives in registers per wave (5 kt x 2 s fragments =
+//     40 VGPR/lane), straight from global;
 //   * single-pass softmax (all <= 80 keys at once - no online rescale);
 //   * causal masking skips whole 16-key tiles above the diagonal.
+// Strip-per-wave keeps 5x the waves of a wave-per-(b,h) layout in flight at
+// the same LDS footprint per workgroup (12 KiB V image + 5 x 2.77 KiB P
+// tiles = 25.8 KiB); the serial layout topped out at 2 waves/SIMD and was
+// latency-exposed.
 // D = 64 only (every model-zoo tower with L <= 80 has head_dim 64).
 // ---------------------------------------------------------------------------
 
@@ -310,9 +304,7 @@ template <bool CAUSAL>
 __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     bf16* __restrict__ o, float* __restrict__ lse, int Lq, int Lk, float scale, int H,
-    int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-    int64_t v_sb, int64_t v_sh, int64_t v_sl, int64_t o_sb, int64_t o_sh, int64_t o_sl,
-    int64_t BH) {
+    hstride q_s, hstride k_s, hstride v_s, hstride o_s) {
   constexpr int D = 64;
   constexpr int LP = 96;       // padded key count (block images need 32-multiples)
   constexpr int PPITCH = 88;   // P-tile pitch. The PV A-frag reads key columns
@@ -326,13 +318,6 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
   constexpr int PSTRIDE = 16 * PPITCH + 8;  // +8 zeroed shorts: the last row's
                                             // col-95 over-read stays in zeroed
                                             // LDS even for the last wave
-  // One 5-wave workgroup per (b, h): wave w owns q-strip w (<= 5 strips at
-  // L <= 80), the V block image is staged ONCE and shared (one barrier).
-  // K lives in REGISTERS per wave (5 kt x 2 s fragments = 40 VGPR/lane).
-  // The previous wave-per-(b,h) version looped the 5 strips serially in
-  // one wave and topped out at 2 waves/SIMD — latency-exposed (68.8 TF/s
-  // at CLIP-text L=77); strip-per-wave runs 5x the waves at the same LDS
-  // footprint per WG (12 KiB V image + 5 x 2.77 KiB P tiles = 25.8 KiB).
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int wave = threadIdx.x / WAVE;
   const int lane = threadIdx.x % WAVE;
@@ -347,13 +332,12 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
 #pragma unroll
   for (int i = 0; i < (PSTRIDE / 8 + WAVE - 1) / WAVE; ++i) {
     const int idx = i * WAVE + lane;
-    if (idx < PSTRIDE / 8) *reinterpret_cast<bf16x8_t*>(pt + idx * 8) = bf16x8_t{};
+    if (idx < PSTRIDE / 8) *reinterpret_cast<bf16x8*>(pt + idx * 8) = bf16x8{};
   }
-  const int64_t b = bh / H, h = bh % H;
-  const bf16* qp = q + b * q_sb + h * q_sh;
-  const bf16* kp = k + b * k_sb + h * k_sh;
-  const bf16* vp = v + b * v_sb + h * v_sh;
-  bf16* op = o + b * o_sb + h * o_sh;
+  const bf16* qp = head_ptr(q, q_s, bh, H);
+  const bf16* kp = head_ptr(k, k_s, bh, H);
+  const bf16* vp = head_ptr(v, v_s, bh, H);
+  bf16* op = head_ptr(o, o_s, bh, H);
 
   // ---- stage V into the workgroup's shared block image (zero-padded) -----
   {
@@ -361,9 +345,9 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
     for (int idx = t; idx < LP * D / 8; idx += 320) {  // 8-short chunk: (key, d-oct)
       const int key = idx >> 3;
       const int d8 = (idx & 7) * 8;
-      bf16x8_t vv_{};
-      if (key < Lk) vv_ = *reinterpret_cast<const bf16x8_t*>(vp + (int64_t)key * v_sl + d8);
-      *reinterpret_cast<bf16x8_t*>(vb + boff<D>(key, d8)) = vv_;
+      bf16x8 vv_{};
+      if (key < Lk) vv_ = *reinterpret_cast<const bf16x8*>(vp + (int64_t)key * v_s.l + d8);
+      *reinterpret_cast<bf16x8*>(vb + boff<D>(key, d8)) = vv_;
     }
   }
   const int nq = (Lq + 15) / 16;
@@ -375,23 +359,23 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
     // ---- K fragments straight from global into registers (causal strips
     // stop at their diagonal tile) -----------------------------------------
     const int ktmax0 = CAUSAL ? min(nkt, qs + 1) : nkt;
-    bf16x8_t kfr[5][2];
+    bf16x8 kfr[5][2];
 #pragma unroll
     for (int kt = 0; kt < 5; ++kt) {
       const int key = 16 * kt + lo;
 #pragma unroll
       for (int s = 0; s < 2; ++s)
         kfr[kt][s] = (kt < ktmax0 && key < Lk)
-                         ? *reinterpret_cast<const bf16x8_t*>(kp + (int64_t)key * k_sl + 32 * s + hi * 8)
-                         : bf16x8_t{};
+                         ? *reinterpret_cast<const bf16x8*>(kp + (int64_t)key * k_s.l + 32 * s + hi * 8)
+                         : bf16x8{};
     }
     const int qrow = min(q0 + lo, Lq - 1);
-    const bf16x8_t qb0 = *reinterpret_cast<const bf16x8_t*>(qp + (int64_t)qrow * q_sl + hi * 8);
-    const bf16x8_t qb1 = *reinterpret_cast<const bf16x8_t*>(qp + (int64_t)qrow * q_sl + 32 + hi * 8);
+    const bf16x8 qb0 = *reinterpret_cast<const bf16x8*>(qp + (int64_t)qrow * q_s.l + hi * 8);
+    const bf16x8 qb1 = *reinterpret_cast<const bf16x8*>(qp + (int64_t)qrow * q_s.l + 32 + hi * 8);
 
     // ---- S^T = K . Q^T over <= 5 16-key tiles ----------------------------
     const int ktmax = ktmax0;
-    f32x4_t sc[5] = {};
+    f32x4 sc[5] = {};
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kt = 0; kt < 5; ++kt) {
@@ -439,15 +423,15 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
     }
 
     // ---- O = P . V (A = P rows, B = V^T via tr reads) --------------------
-    f32x4_t acc_o[4] = {};
+    f32x4 acc_o[4] = {};
     const int kv_hi = CAUSAL ? min(Lk, q0 + 16) : Lk;
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
       if (32 * s >= kv_hi) continue;
-      bf16x8_t vbf[4];
+      bf16x8 vbf[4];
       const lds_cp bbase = (lds_cp)(const void*)(vb + s * 32 * D) + lane * 8;
       tr_frag_x4(bbase, vbf);
-      const bf16x8_t pa = *reinterpret_cast<const bf16x8_t*>(pt + lo * PPITCH + 32 * s + hi * 8);
+      const bf16x8 pa = row_frag(pt, lo, PPITCH, s, hi);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) acc_o[dt] = MFMA16(pa, vbf[dt], acc_o[dt]);
@@ -465,7 +449,7 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
       if (qr >= Lq) continue;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
-        op[(int64_t)qr * o_sl + 16 * dt + lo] = f2bf(acc_o[dt][r] * invl_r[r]);
+        op[(int64_t)qr * o_s.l + 16 * dt + lo] = f2bf(acc_o[dt][r] * invl_r[r]);
     }
     if (hi == 0 && q0 + lo < Lq) lse[bh * Lq + q0 + lo] = mt + __logf(psum);
   }
@@ -475,83 +459,41 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
 
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     bool causal, double scale) {
-  // q,k,v: (B,H,L,64) views whose innermost dim is contiguous, head stride
-  // is 64 and L-row stride is uniform — covers both contiguous BHLD and the
-  // un-copied (B,L,H,64) / fused-qkv (B,L,3,H,64) layouts.
-  TORCH_CHECK(q.is_cuda());
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn_fwd: bf16 only, got ", q.scalar_type());
-  TORCH_CHECK(q.dim() == 4, "attn_fwd: (B,H,L,D) expected");
+  // q,k,v: (B,H,L,D) views whose innermost dim is contiguous — covers both
+  // contiguous BHLD and the un-copied (B,L,H,D) / fused-qkv (B,L,3,H,D)
+  // layouts.
+  check_attn_args("attn_fwd", {{"q", q}}, {{"k", k}, {"v", v}});
   const int Dr = q.size(3);
-  TORCH_CHECK(Dr == 64 || Dr == 72 || Dr == 80 || Dr == 96 || Dr == 128,
-              "attn_fwd: head_dim must be one of {64,72,80,96,128}, got ", Dr);
   const int DP = Dr <= 64 ? 64 : (Dr <= 96 ? 96 : 128);
   const int B = q.size(0), H = q.size(1), Lq = q.size(2), Lk = k.size(2);
-  TORCH_CHECK(k.size(0) == B && k.size(1) == H && v.size(2) == Lk);
-  for (auto* t : {&q, &k, &v})
-    TORCH_CHECK(t->stride(3) == 1, "attn_fwd: innermost dim must be contiguous");
-  // O written in (B,L,H,64) memory order so the model's (B,L,H*64) reshape is
+  // O written in (B,L,H,D) memory order so the model's (B,L,H*D) reshape is
   // a free view (no permute copy)
-  auto o_storage = torch::empty({B, Lq, H, Dr}, q.options());
-  auto o = o_storage.permute({0, 2, 1, 3});
+  auto o = torch::empty({B, Lq, H, Dr}, q.options()).permute({0, 2, 1, 3});
   auto lse = torch::empty({B, H, Lq}, q.options().dtype(torch::kFloat32));
-  // 2 strips everywhere (3 waves/SIMD occupancy): the early-r02 measurement
-  // that had 4 winning at L=197 no longer holds after the block-image /
-  // double-buffer rework (L=197: 160 -> 171 TF/s at nstrip 2; L=257 with 4
-  // is far worse, 207 -> 168). JIMM_AMD_ATTN_NSTRIP overrides for A/B.
-  const int ntq = (Lq + QBLK - 1) / QBLK;
-  int nstrip = 2;
-  if (DP == 64) {
-    if (const char* e = getenv("JIMM_AMD_ATTN_NSTRIP")) nstrip = (std::string(e) == "2") ? 2 : 4;
-  }
-  const dim3 grid((ntq + nstrip - 1) / nstrip, (unsigned)((int64_t)B * H));
-  const size_t shmem =
-      (2 * (KVBLK * DP + KVBLK * (DP + 8)) + 4 * 16 * (DP + 8)) * sizeof(short);
+  const unsigned BH = (unsigned)((int64_t)B * H);
   auto stream = at::hip::getCurrentHIPStream();
-#define ATTN_ARGS                                                                          \
-                     reinterpret_cast<const bf16*>(q.data_ptr()),                          \
-                     reinterpret_cast<const bf16*>(k.data_ptr()),                          \
-                     reinterpret_cast<const bf16*>(v.data_ptr()),                          \
-                     reinterpret_cast<bf16*>(o_storage.data_ptr()), lse.data_ptr<float>(), \
-                     Lq, Lk, (float)scale, H, Dr, q.stride(0), q.stride(1), q.stride(2),   \
-                     k.stride(0), k.stride(1), k.stride(2),                                \
-                     v.stride(0), v.stride(1), v.stride(2),                                \
-                     o.stride(0), o.stride(1), o.stride(2)
-  // small-L fast path: one wave per (b,h), no barriers (L <= 80, D = 64)
-  if (Dr == 64 && Lq == Lk && Lk <= 80) {
-    const int64_t BH = (int64_t)B * H;
-    const dim3 sgrid((unsigned)BH);  // one 5-wave WG per (b, h)
-    const size_t sshmem = (96 * 64 + 5 * (16 * 88 + 8)) * sizeof(short);
-#define SMALL_ARGS                                                                         \
-                     reinterpret_cast<const bf16*>(q.data_ptr()),                          \
-                     reinterpret_cast<const bf16*>(k.data_ptr()),                          \
-                     reinterpret_cast<const bf16*>(v.data_ptr()),                          \
-                     reinterpret_cast<bf16*>(o_storage.data_ptr()), lse.data_ptr<float>(), \
-                     Lq, Lk, (float)scale, H, q.stride(0), q.stride(1), q.stride(2),       \
-                     k.stride(0), k.stride(1), k.stride(2),                                \
-                     v.stride(0), v.stride(1), v.stride(2),                                \
-                     o.stride(0), o.stride(1), o.stride(2), BH
-    if (causal)
-      hipLaunchKernelGGL((attn_fwd_small_kernel<true>), sgrid, dim3(320), sshmem, stream,
-                         SMALL_ARGS);
-    else
-      hipLaunchKernelGGL((attn_fwd_small_kernel<false>), sgrid, dim3(320), sshmem, stream,
-                         SMALL_ARGS);
-#undef SMALL_ARGS
-    return {o, lse};
-  }
-#define ATTN_LAUNCH(C)                                                                     \
-  do {                                                                                     \
-    if (DP == 128)                                                                         \
-      launch_lds<attn_fwd_kernel<C, 2, 128>>(grid, dim3(256), shmem, shmem, stream, ATTN_ARGS); \
-    else if (DP == 96)                                                                     \
-      launch_lds<attn_fwd_kernel<C, 2, 96>>(grid, dim3(256), shmem, shmem, stream, ATTN_ARGS);  \
-    else if (nstrip == 2)                                                                  \
-      launch_lds<attn_fwd_kernel<C, 2, 64>>(grid, dim3(256), shmem, shmem, stream, ATTN_ARGS);  \
-    else                                                                                   \
-      launch_lds<attn_fwd_kernel<C, 4, 64>>(grid, dim3(256), shmem, shmem, stream, ATTN_ARGS);  \
-  } while (0)
-  if (causal) ATTN_LAUNCH(true); else ATTN_LAUNCH(false);
-#undef ATTN_LAUNCH
-#undef ATTN_ARGS
+  with_flags(
+      [&](auto c) {
+        constexpr bool C = decltype(c)::value;
+        // small-L fast path: one 5-wave workgroup per (b,h) (L <= 80, D = 64)
+        if (Dr == 64 && Lq == Lk && Lk <= 80) {
+          const size_t shmem = (96 * 64 + 5 * (16 * 88 + 8)) * sizeof(short);
+          launch_lds<attn_fwd_small_kernel<C>>(
+              dim3(BH), dim3(320), shmem, shmem, stream, bf16_ptr(q), bf16_ptr(k), bf16_ptr(v),
+              bf16_ptr(o), lse.data_ptr<float>(), Lq, Lk, (float)scale, H, hstrides(q),
+              hstrides(k), hstrides(v), hstrides(o));
+          return;
+        }
+        const int ntq = (Lq + QBLK - 1) / QBLK;
+        const size_t shmem =
+            (2 * (KVBLK * DP + KVBLK * (DP + 8)) + 4 * 16 * (DP + 8)) * sizeof(short);
+        with_int<64, 96, 128>(DP, "padded head dim", [&](auto dp) {
+          launch_lds<attn_fwd_kernel<C, decltype(dp)::value>>(
+              dim3((ntq + NSTRIP - 1) / NSTRIP, BH), dim3(256), shmem, shmem, stream,
+              bf16_ptr(q), bf16_ptr(k), bf16_ptr(v), bf16_ptr(o), lse.data_ptr<float>(), Lq, Lk,
+              (float)scale, H, Dr, hstrides(q), hstrides(k), hstrides(v), hstrides(o));
+        });
+      },
+      causal);
   return {o, lse};
 }

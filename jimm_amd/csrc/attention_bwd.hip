@@ -15,8 +15,6 @@
 
 namespace {
 
-typedef short short8_t __attribute__((ext_vector_type(8)));
-
 template <bool CAUSAL>
 __global__ void attn_bwd_p_kernel(bf16* __restrict__ s, const float* __restrict__ lse,
                                   int64_t nrows, int Lk, float scale) {
@@ -39,14 +37,14 @@ __global__ void attn_bwd_p_kernel(bf16* __restrict__ s, const float* __restrict_
       sr[c] = f2bf(p);
     }
     for (int c = head + lane * 8; c < Lv; c += WAVE * 8) {
-      short8_t v = *reinterpret_cast<const short8_t*>(sr + c);
+      bf16x8 v = *reinterpret_cast<const bf16x8*>(sr + c);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float p = __expf(bfs2f(v[j]) * scale - l);
         if (CAUSAL && c + j > qi) p = 0.f;
         v[j] = f2bfs(p);
       }
-      *reinterpret_cast<short8_t*>(sr + c) = v;
+      *reinterpret_cast<bf16x8*>(sr + c) = v;
     }
     for (int c = Lv + lane; c < Lk; c += WAVE) {
       float p = __expf(bf2f(sr[c]) * scale - l);
@@ -88,12 +86,12 @@ __global__ void attn_ds_kernel(bf16* __restrict__ dp, const bf16* __restrict__ p
     for (int c = lane; c < head; c += WAVE)
       dpr[c] = f2bf(bf2f(pr[c]) * (bf2f(dpr[c]) - dv) * scale);
     for (int c = head + lane * 8; c < Lv; c += WAVE * 8) {
-      short8_t a = *reinterpret_cast<const short8_t*>(dpr + c);
-      short8_t b = *reinterpret_cast<const short8_t*>(pr + c);
+      bf16x8 a = *reinterpret_cast<const bf16x8*>(dpr + c);
+      bf16x8 b = *reinterpret_cast<const bf16x8*>(pr + c);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         a[j] = f2bfs(bfs2f(b[j]) * (bfs2f(a[j]) - dv) * scale);
-      *reinterpret_cast<short8_t*>(dpr + c) = a;
+      *reinterpret_cast<bf16x8*>(dpr + c) = a;
     }
     for (int c = Lv + lane; c < Lk; c += WAVE)
       dpr[c] = f2bf(bf2f(pr[c]) * (bf2f(dpr[c]) - dv) * scale);

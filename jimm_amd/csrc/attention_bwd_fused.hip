@@ -37,18 +37,16 @@
 
 namespace {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int BLK = 64;            // q rows / keys per workgroup tile
 
 // Head dims beyond 64: padded-D template DP in {64,96,128}, ragged chunks
-// guarded by ld8g<DP> (mfma.h). DP=64 keeps the round-1 fast path
-// (NKV=2 / NQS=2 with cached fragments); DP>64 uses 1 tile per workgroup
-// with inline fragment reads to stay inside the register budget.
-//
+// guarded by ld8g<DP> (mfma.h). A tiled workgroup owns 2 tiles at DP=64,
+// with the staged tile's fragments cached across them; DP>64 owns 1 tile and
+// reads the fragments inline to stay inside the register budget.
+constexpr int tiles_per_wg(int DP) { return DP == 64 ? 2 : 1; }
+
 // Transposed operands come from block-format images: boff<ND> places an
-// element, tr_frag_x4 / tr_frag_x2 read the fragments back (mfma.h).
+// element, tr_frags / tr_frag_x4 read the fragments back (mfma.h).
 
 // ---------------------------------------------------------------------------
 // D = rowsum(dO * O), stride-aware
@@ -56,8 +54,7 @@ constexpr int BLK = 64;            // q rows / keys per workgroup tile
 
 __global__ void attn_d2_kernel(const bf16* __restrict__ dO, const bf16* __restrict__ O,
                                float* __restrict__ Dv, int H, int L, int Dr, int64_t nrows,
-                               int64_t do_sb, int64_t do_sh, int64_t do_sl,
-                               int64_t o_sb, int64_t o_sh, int64_t o_sl) {
+                               hstride do_s, hstride o_s) {
   // 8 rows per wave (all 64 lanes loading): lane -> (sub-row l>>3, 8 cols)
   const int wave = threadIdx.x / WAVE;
   const int lane = threadIdx.x % WAVE;
@@ -71,8 +68,8 @@ __global__ void attn_d2_kernel(const bf16* __restrict__ dO, const bf16* __restri
     const int64_t b = rc / ((int64_t)H * L);
     const int h = (int)((rc / L) % H);
     const int l = (int)(rc % L);
-    const bf16* a = dO + b * do_sb + h * do_sh + (int64_t)l * do_sl;
-    const bf16* o = O + b * o_sb + h * o_sh + (int64_t)l * o_sl;
+    const bf16* a = dO + b * do_s.b + h * do_s.h + (int64_t)l * do_s.l;
+    const bf16* o = O + b * o_s.b + h * o_s.h + (int64_t)l * o_s.l;
     float acc = 0.f;
     for (int cg = 0; cg < Dr; cg += 64) {
       if (cg + c0 + 8 > Dr) continue;
@@ -93,25 +90,22 @@ __global__ void attn_d2_kernel(const bf16* __restrict__ dO, const bf16* __restri
 // dK/dV kernel: workgroup owns keys [kv0, kv0+64); loops q tiles
 // ---------------------------------------------------------------------------
 
-template <bool CAUSAL, int NKV, int DP>
+template <bool CAUSAL, int DP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     const bf16* __restrict__ dO, const float* __restrict__ lse, const float* __restrict__ Dv,
     bf16* __restrict__ dk, bf16* __restrict__ dv, int Lq, int Lk, float scale, int H,
-    int Dr,
-    int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-    int64_t v_sb, int64_t v_sh, int64_t v_sl, int64_t do_sb, int64_t do_sh, int64_t do_sl,
-    int64_t dk_sb, int64_t dk_sh, int64_t dk_sl, int64_t dv_sb, int64_t dv_sh, int64_t dv_sl) {
-  // v3: each workgroup owns up to NKV kv tiles (cyclic tile mapping, like
-  // the forward kernel) so the Q/dO images are staged ONCE for all of them
-  // (v2 staged them once per kv-tile workgroup: 4x redundant at L=197).
+    int Dr, hstride q_s, hstride k_s, hstride v_s, hstride do_s, hstride dk_s, hstride dv_s) {
+  // Each workgroup owns up to NKV kv tiles (cyclic tile mapping, like the
+  // forward kernel) so the Q/dO images are staged ONCE for all of them (one
+  // kv tile per workgroup is 4x redundant staging at L=197).
   // K/V live as per-strip A-FRAGMENTS in registers — no K/V LDS at all.
   // LDS: Q^T/dO^T (transposed) + Q/dO (row) images of the current q tile,
   // per-wave P/dS tile. ~46 KiB.
+  constexpr int NKV = tiles_per_wg(DP);
   constexpr int PITCH = DP + 8;
   constexpr int NS = DP / 32;
   constexpr int NT = DP / 16;
-  constexpr int NCG = (DP + 63) / 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // staging images are DOUBLE-buffered: the write pass for tile it+1 runs
   // before/under tile it's MFMAs into the other buffer, so each q-tile
@@ -129,13 +123,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
   const int lane = tid % WAVE;
   const int lo = lane & 15, hi = lane >> 4;
   const int64_t bh = blockIdx.y;
-  const int64_t b = bh / H, h = bh % H;
   const int ntk = (Lk + BLK - 1) / BLK;
 
-  const bf16* qp = q + b * q_sb + h * q_sh;
-  const bf16* kp = k + b * k_sb + h * k_sh;
-  const bf16* vp = v + b * v_sb + h * v_sh;
-  const bf16* dop = dO + b * do_sb + h * do_sh;
+  const bf16* qp = head_ptr(q, q_s, bh, H);
+  const bf16* kp = head_ptr(k, k_s, bh, H);
+  const bf16* vp = head_ptr(v, v_s, bh, H);
+  const bf16* dop = head_ptr(dO, do_s, bh, H);
   const float* lsep = lse + bh * Lq;
   const float* dvp_row = Dv + bh * Lq;
 
@@ -143,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
   // strip s covers kv tile ti(s) = blockIdx.x + s*gridDim.x; this wave's 16
   // keys of that tile: rows 16*wave + lo. Invalid rows clamp; their P/dS
   // contributions are masked to zero and their stores are guarded.
-  bf16x8_t ka[NKV][NS], va[NKV][NS];
+  bf16x8 ka[NKV][NS], va[NKV][NS];
   int kvbase[NKV];
   int nactive = 0;
 #pragma unroll
@@ -154,24 +147,25 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
     const int key = min(min(ti, ntk - 1) * BLK + 16 * wave + lo, Lk - 1);
 #pragma unroll
     for (int t = 0; t < NS; ++t) {
-      ka[s][t] = ld8g<DP>(kp + (int64_t)key * k_sl, 32 * t + hi * 8, Dr);
-      va[s][t] = ld8g<DP>(vp + (int64_t)key * v_sl, 32 * t + hi * 8, Dr);
+      ka[s][t] = ld8g<DP>(kp + (int64_t)key * k_s.l, 32 * t + hi * 8, Dr);
+      va[s][t] = ld8g<DP>(vp + (int64_t)key * v_s.l, 32 * t + hi * 8, Dr);
     }
   }
 
   short* my_p = p_lds + wave * 16 * PITCH;
 
-  f32x4_t acc_dk[NKV][NT] = {};  // rows key = 16*wave + hi*4+r, cols d = 16*dt+lo
-  f32x4_t acc_dv[NKV][NT] = {};
+  f32x4 acc_dk[NKV][NT] = {};  // rows key = 16*wave + hi*4+r, cols d = 16*dt+lo
+  f32x4 acc_dv[NKV][NT] = {};
 
   // causal: the earliest kv tile of this WG bounds the first useful q tile
   const int q_start = CAUSAL ? (kvbase[0] / BLK) * BLK : 0;
   const int ntiles = (Lq - q_start + BLK - 1) / BLK;
 
   // per-thread staging slot for the Q/dO images
+  constexpr int NCG = (DP + 63) / 64;
   const int st_row = tid / 4;
   const int st_c0 = (tid % 4) * 16;
-  bf16x8_t qreg[NCG][2], doreg[NCG][2];
+  bf16x8 qreg[NCG][2], doreg[NCG][2];
   bool st_valid;
   auto load_stage_regs = [&](int q0) {
     const int qi = q0 + st_row;
@@ -182,8 +176,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
       if (cg * 64 + st_c0 >= DP) continue;
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
-        qreg[cg][hh] = ld8g<DP>(qp + (int64_t)qr * q_sl, cg * 64 + st_c0 + hh * 8, Dr);
-        doreg[cg][hh] = ld8g<DP>(dop + (int64_t)qr * do_sl, cg * 64 + st_c0 + hh * 8, Dr);
+        qreg[cg][hh] = ld8g<DP>(qp + (int64_t)qr * q_s.l, cg * 64 + st_c0 + hh * 8, Dr);
+        doreg[cg][hh] = ld8g<DP>(dop + (int64_t)qr * do_s.l, cg * 64 + st_c0 + hh * 8, Dr);
       }
     }
   };
@@ -195,12 +189,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
       if (c0 >= DP) continue;
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
-        const bf16x8_t qv = st_valid ? qreg[cg][hh] : bf16x8_t{};
-        const bf16x8_t dv2 = st_valid ? doreg[cg][hh] : bf16x8_t{};
-        *reinterpret_cast<bf16x8_t*>(qr_lds + bo + st_row * PITCH + c0 + hh * 8) = qv;
-        *reinterpret_cast<bf16x8_t*>(dor_lds + bo + st_row * PITCH + c0 + hh * 8) = dv2;
-        *reinterpret_cast<bf16x8_t*>(qb_lds + bo + boff<DP>(st_row, c0 + hh * 8)) = qv;
-        *reinterpret_cast<bf16x8_t*>(dob_lds + bo + boff<DP>(st_row, c0 + hh * 8)) = dv2;
+        const bf16x8 qv = st_valid ? qreg[cg][hh] : bf16x8{};
+        const bf16x8 dv2 = st_valid ? doreg[cg][hh] : bf16x8{};
+        *reinterpret_cast<bf16x8*>(qr_lds + bo + st_row * PITCH + c0 + hh * 8) = qv;
+        *reinterpret_cast<bf16x8*>(dor_lds + bo + st_row * PITCH + c0 + hh * 8) = dv2;
+        *reinterpret_cast<bf16x8*>(qb_lds + bo + boff<DP>(st_row, c0 + hh * 8)) = qv;
+        *reinterpret_cast<bf16x8*>(dob_lds + bo + boff<DP>(st_row, c0 + hh * 8)) = dv2;
       }
     }
   };
@@ -221,14 +215,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
     // every kv strip) ------------------------------------------------------
     // DP==64 caches the q-tile fragments across the NKV strips; larger DP
     // reads them inline per use (the 4xNS cache would spill at NS=4)
-    bf16x8_t qb[DP == 64 ? 4 : 1][NS], dob[DP == 64 ? 4 : 1][NS];
+    bf16x8 qb[DP == 64 ? 4 : 1][NS], dob[DP == 64 ? 4 : 1][NS];
     if constexpr (DP == 64) {
 #pragma unroll
       for (int qt = 0; qt < 4; ++qt) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          qb[qt][s] = *reinterpret_cast<const bf16x8_t*>(qr_lds + sbo + (16 * qt + lo) * PITCH + 32 * s + hi * 8);
-          dob[qt][s] = *reinterpret_cast<const bf16x8_t*>(dor_lds + sbo + (16 * qt + lo) * PITCH + 32 * s + hi * 8);
+          qb[qt][s] = row_frag(qr_lds + sbo, 16 * qt + lo, PITCH, s, hi);
+          dob[qt][s] = row_frag(dor_lds + sbo, 16 * qt + lo, PITCH, s, hi);
         }
       }
     }
@@ -261,17 +255,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
           continue;
         }
         __builtin_amdgcn_s_setprio(1);
-        f32x4_t sc = {};
-        f32x4_t dpc = {};
+        f32x4 sc = {};
+        f32x4 dpc = {};
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          bf16x8_t qf, dof;
+          bf16x8 qf, dof;
           if constexpr (DP == 64) {
             qf = qb[qt][s];
             dof = dob[qt][s];
           } else {
-            qf = *reinterpret_cast<const bf16x8_t*>(qr_lds + sbo + (16 * qt + lo) * PITCH + 32 * s + hi * 8);
-            dof = *reinterpret_cast<const bf16x8_t*>(dor_lds + sbo + (16 * qt + lo) * PITCH + 32 * s + hi * 8);
+            qf = row_frag(qr_lds + sbo, 16 * qt + lo, PITCH, s, hi);
+            dof = row_frag(dor_lds + sbo, 16 * qt + lo, PITCH, s, hi);
           }
           sc = MFMA16(ka[sidx][s], qf, sc);
           dpc = MFMA16(va[sidx][s], dof, dpc);
@@ -298,12 +292,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if ((CAUSAL && q0 + 32 * s + 31 < key_min) || q0 + 32 * s >= Lq) continue;
-        bf16x8_t bfr[NT];
-        const lds_cp bbase = (lds_cp)(const void*)(dob_lds + sbo + s * 32 * DP) + lane * 8;
-        tr_frag_x4(bbase, *reinterpret_cast<bf16x8_t(*)[4]>(&bfr[0]));
-        if constexpr (NT == 6) tr_frag_x2(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[2]>(&bfr[4]));
-        if constexpr (NT == 8) tr_frag_x4(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[4]>(&bfr[4]));
-        const bf16x8_t pa = *reinterpret_cast<const bf16x8_t*>(my_p + lo * PITCH + 32 * s + hi * 8);
+        bf16x8 bfr[NT];
+        tr_frags<NT>((lds_cp)(const void*)(dob_lds + sbo + s * 32 * DP) + lane * 8, bfr);
+        const bf16x8 pa = row_frag(my_p, lo, PITCH, s, hi);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int dt = 0; dt < NT; ++dt) acc_dv[sidx][dt] = MFMA16(pa, bfr[dt], acc_dv[sidx][dt]);
@@ -319,12 +310,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if ((CAUSAL && q0 + 32 * s + 31 < key_min) || q0 + 32 * s >= Lq) continue;
-        bf16x8_t bfr[NT];
-        const lds_cp bbase = (lds_cp)(const void*)(qb_lds + sbo + s * 32 * DP) + lane * 8;
-        tr_frag_x4(bbase, *reinterpret_cast<bf16x8_t(*)[4]>(&bfr[0]));
-        if constexpr (NT == 6) tr_frag_x2(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[2]>(&bfr[4]));
-        if constexpr (NT == 8) tr_frag_x4(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[4]>(&bfr[4]));
-        const bf16x8_t dsa = *reinterpret_cast<const bf16x8_t*>(my_p + lo * PITCH + 32 * s + hi * 8);
+        bf16x8 bfr[NT];
+        tr_frags<NT>((lds_cp)(const void*)(qb_lds + sbo + s * 32 * DP) + lane * 8, bfr);
+        const bf16x8 dsa = row_frag(my_p, lo, PITCH, s, hi);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int dt = 0; dt < NT; ++dt) acc_dk[sidx][dt] = MFMA16(dsa, bfr[dt], acc_dk[sidx][dt]);
@@ -338,8 +326,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
   }
 
   // ---- store dK, dV (strided, bf16) ---------------------------------------
-  bf16* dkp = dk + b * dk_sb + h * dk_sh;
-  bf16* dvp = dv + b * dv_sb + h * dv_sh;
+  bf16* dkp = head_ptr(dk, dk_s, bh, H);
+  bf16* dvp = head_ptr(dv, dv_s, bh, H);
 #pragma unroll
   for (int sidx = 0; sidx < NKV; ++sidx) {
     if (sidx >= nactive) continue;
@@ -350,8 +338,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
 #pragma unroll
       for (int dt = 0; dt < NT; ++dt) {
         if (DP != 64 && 16 * dt + lo >= Dr) continue;
-        dkp[(int64_t)key * dk_sl + 16 * dt + lo] = f2bf(acc_dk[sidx][dt][r]);
-        dvp[(int64_t)key * dv_sl + 16 * dt + lo] = f2bf(acc_dv[sidx][dt][r]);
+        dkp[(int64_t)key * dk_s.l + 16 * dt + lo] = f2bf(acc_dk[sidx][dt][r]);
+        dvp[(int64_t)key * dv_s.l + 16 * dt + lo] = f2bf(acc_dv[sidx][dt][r]);
       }
     }
   }
@@ -361,22 +349,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
 // dQ kernel: workgroup owns q rows [q0, q0+64); loops kv tiles
 // ---------------------------------------------------------------------------
 
-template <bool CAUSAL, int NQS, int DP>
+template <bool CAUSAL, int DP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     const bf16* __restrict__ dO, const float* __restrict__ lse, const float* __restrict__ Dv,
-    bf16* __restrict__ dq, int Lq, int Lk, float scale, int H, int Dr,
-    int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-    int64_t v_sb, int64_t v_sh, int64_t v_sl, int64_t do_sb, int64_t do_sh, int64_t do_sl,
-    int64_t dq_sb, int64_t dq_sh, int64_t dq_sl) {
-  // v3: each workgroup owns up to NQS q tiles (cyclic mapping) so the K
-  // images are staged ONCE for all of them; Q/dO A-fragments live in
-  // registers per strip. LDS: K^T + K/V row images of the current kv tile,
-  // per-wave dS tile.
+    bf16* __restrict__ dq, int Lq, int Lk, float scale, int H, int Dr, hstride q_s,
+    hstride k_s, hstride v_s, hstride do_s, hstride dq_s) {
+  // Each workgroup owns up to NQS q tiles (cyclic mapping) so the K images
+  // are staged ONCE for all of them; Q/dO A-fragments live in registers per
+  // strip. LDS: K^T + K/V row images of the current kv tile, per-wave dS
+  // tile.
+  constexpr int NQS = tiles_per_wg(DP);
   constexpr int PITCH = DP + 8;
   constexpr int NS = DP / 32;
   constexpr int NT = DP / 16;
-  constexpr int NCG = (DP + 63) / 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // double-buffered staging (as in the dkv kernel): one barrier per tile
   constexpr int IMGSQ = BLK * DP + 2 * BLK * PITCH;  // per buffer
@@ -390,20 +376,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
   const int lane = tid % WAVE;
   const int lo = lane & 15, hi = lane >> 4;
   const int64_t bh = blockIdx.y;
-  const int64_t b = bh / H, h = bh % H;
   const int ntq = (Lq + BLK - 1) / BLK;
 
-  const bf16* qp = q + b * q_sb + h * q_sh;
-  const bf16* kp = k + b * k_sb + h * k_sh;
-  const bf16* vp = v + b * v_sb + h * v_sh;
-  const bf16* dop = dO + b * do_sb + h * do_sh;
+  const bf16* qp = head_ptr(q, q_s, bh, H);
+  const bf16* kp = head_ptr(k, k_s, bh, H);
+  const bf16* vp = head_ptr(v, v_s, bh, H);
+  const bf16* dop = head_ptr(dO, do_s, bh, H);
   const float* lsep = lse + bh * Lq;
   const float* dvp_row = Dv + bh * Lq;
 
   // ---- per-strip Q/dO A-fragments + per-row lse/D -------------------------
   // strip s covers q tile ti(s) = blockIdx.x + s*gridDim.x; this wave's 16
   // q rows of that tile: rows 16*wave + ...
-  bf16x8_t qa[NQS][NS], doa[NQS][NS];
+  bf16x8 qa[NQS][NS], doa[NQS][NS];
   float lse_r[NQS][4], d_r[NQS][4];
   int qbase[NQS];
   int nactive = 0;
@@ -416,8 +401,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
     const int qrow = min(q0 + lo, Lq - 1);
 #pragma unroll
     for (int t = 0; t < NS; ++t) {
-      qa[s][t] = ld8g<DP>(qp + (int64_t)qrow * q_sl, 32 * t + hi * 8, Dr);
-      doa[s][t] = ld8g<DP>(dop + (int64_t)qrow * do_sl, 32 * t + hi * 8, Dr);
+      qa[s][t] = ld8g<DP>(qp + (int64_t)qrow * q_s.l, 32 * t + hi * 8, Dr);
+      doa[s][t] = ld8g<DP>(dop + (int64_t)qrow * do_s.l, 32 * t + hi * 8, Dr);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -428,16 +413,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
   }
 
   short* my_ds = ds_lds + wave * 16 * PITCH;
-  f32x4_t acc_dq[NQS][NT] = {};  // rows q = hi*4+r, cols d = 16*dt + lo
+  f32x4 acc_dq[NQS][NT] = {};  // rows q = hi*4+r, cols d = 16*dt + lo
 
   // causal: only kv tiles up to the LAST active strip's diagonal are needed
   const int ti_max = blockIdx.x + (nactive - 1) * gridDim.x;
   const int kv_end = CAUSAL ? min(Lk, (ti_max + 1) * BLK) : Lk;
   const int ntiles = (kv_end + BLK - 1) / BLK;
 
+  constexpr int NCG = (DP + 63) / 64;
   const int st_row = tid / 4;
   const int st_c0 = (tid % 4) * 16;
-  bf16x8_t kreg[NCG][2], vreg[NCG][2];
+  bf16x8 kreg[NCG][2], vreg[NCG][2];
   bool st_valid;
   auto load_stage_regs = [&](int kv0) {
     const int key = kv0 + st_row;
@@ -448,8 +434,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
       if (cg * 64 + st_c0 >= DP) continue;
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
-        kreg[cg][hh] = ld8g<DP>(kp + (int64_t)kr * k_sl, cg * 64 + st_c0 + hh * 8, Dr);
-        vreg[cg][hh] = ld8g<DP>(vp + (int64_t)kr * v_sl, cg * 64 + st_c0 + hh * 8, Dr);
+        kreg[cg][hh] = ld8g<DP>(kp + (int64_t)kr * k_s.l, cg * 64 + st_c0 + hh * 8, Dr);
+        vreg[cg][hh] = ld8g<DP>(vp + (int64_t)kr * v_s.l, cg * 64 + st_c0 + hh * 8, Dr);
       }
     }
   };
@@ -461,11 +447,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
       if (c0 >= DP) continue;
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
-        const bf16x8_t kv2 = st_valid ? kreg[cg][hh] : bf16x8_t{};
-        const bf16x8_t vv2 = st_valid ? vreg[cg][hh] : bf16x8_t{};
-        *reinterpret_cast<bf16x8_t*>(kr_lds + bo + st_row * PITCH + c0 + hh * 8) = kv2;
-        *reinterpret_cast<bf16x8_t*>(vr_lds + bo + st_row * PITCH + c0 + hh * 8) = vv2;
-        *reinterpret_cast<bf16x8_t*>(kb_lds + bo + boff<DP>(st_row, c0 + hh * 8)) = kv2;
+        const bf16x8 kv2 = st_valid ? kreg[cg][hh] : bf16x8{};
+        const bf16x8 vv2 = st_valid ? vreg[cg][hh] : bf16x8{};
+        *reinterpret_cast<bf16x8*>(kr_lds + bo + st_row * PITCH + c0 + hh * 8) = kv2;
+        *reinterpret_cast<bf16x8*>(vr_lds + bo + st_row * PITCH + c0 + hh * 8) = vv2;
+        *reinterpret_cast<bf16x8*>(kb_lds + bo + boff<DP>(st_row, c0 + hh * 8)) = kv2;
       }
     }
   };
@@ -483,14 +469,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
       if (it + 2 < ntiles) load_stage_regs(kv0 + 2 * BLK);
     }
     // ---- B-fragments of K^T and V^T from the LDS row images (shared) -----
-    bf16x8_t kb[DP == 64 ? 4 : 1][NS], vb[DP == 64 ? 4 : 1][NS];
+    bf16x8 kb[DP == 64 ? 4 : 1][NS], vb[DP == 64 ? 4 : 1][NS];
     if constexpr (DP == 64) {
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          kb[kt][s] = *reinterpret_cast<const bf16x8_t*>(kr_lds + sbo + (16 * kt + lo) * PITCH + 32 * s + hi * 8);
-          vb[kt][s] = *reinterpret_cast<const bf16x8_t*>(vr_lds + sbo + (16 * kt + lo) * PITCH + 32 * s + hi * 8);
+          kb[kt][s] = row_frag(kr_lds + sbo, 16 * kt + lo, PITCH, s, hi);
+          vb[kt][s] = row_frag(vr_lds + sbo, 16 * kt + lo, PITCH, s, hi);
         }
       }
     }
@@ -516,17 +502,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
           continue;
         }
         __builtin_amdgcn_s_setprio(1);
-        f32x4_t sc = {};
-        f32x4_t dpc = {};
+        f32x4 sc = {};
+        f32x4 dpc = {};
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          bf16x8_t kf, vf;
+          bf16x8 kf, vf;
           if constexpr (DP == 64) {
             kf = kb[kt][s];
             vf = vb[kt][s];
           } else {
-            kf = *reinterpret_cast<const bf16x8_t*>(kr_lds + sbo + (16 * kt + lo) * PITCH + 32 * s + hi * 8);
-            vf = *reinterpret_cast<const bf16x8_t*>(vr_lds + sbo + (16 * kt + lo) * PITCH + 32 * s + hi * 8);
+            kf = row_frag(kr_lds + sbo, 16 * kt + lo, PITCH, s, hi);
+            vf = row_frag(vr_lds + sbo, 16 * kt + lo, PITCH, s, hi);
           }
           sc = MFMA16(qa[sidx][s], kf, sc);
           dpc = MFMA16(doa[sidx][s], vf, dpc);
@@ -549,12 +535,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if ((CAUSAL && kv0 + 32 * s > q_max) || kv0 + 32 * s >= Lk) continue;
-        bf16x8_t bfr[NT];
-        const lds_cp bbase = (lds_cp)(const void*)(kb_lds + sbo + s * 32 * DP) + lane * 8;
-        tr_frag_x4(bbase, *reinterpret_cast<bf16x8_t(*)[4]>(&bfr[0]));
-        if constexpr (NT == 6) tr_frag_x2(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[2]>(&bfr[4]));
-        if constexpr (NT == 8) tr_frag_x4(bbase + 4096, *reinterpret_cast<bf16x8_t(*)[4]>(&bfr[4]));
-        const bf16x8_t dsa = *reinterpret_cast<const bf16x8_t*>(my_ds + lo * PITCH + 32 * s + hi * 8);
+        bf16x8 bfr[NT];
+        tr_frags<NT>((lds_cp)(const void*)(kb_lds + sbo + s * 32 * DP) + lane * 8, bfr);
+        const bf16x8 dsa = row_frag(my_ds, lo, PITCH, s, hi);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int dt = 0; dt < NT; ++dt) acc_dq[sidx][dt] = MFMA16(dsa, bfr[dt], acc_dq[sidx][dt]);
@@ -566,7 +549,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
   }
 
   // ---- store dQ (strided, bf16) -------------------------------------------
-  bf16* dqp = dq + b * dq_sb + h * dq_sh;
+  bf16* dqp = head_ptr(dq, dq_s, bh, H);
 #pragma unroll
   for (int sidx = 0; sidx < NQS; ++sidx) {
     if (sidx >= nactive) continue;
@@ -577,7 +560,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
 #pragma unroll
       for (int dt = 0; dt < NT; ++dt)
         if (DP == 64 || 16 * dt + lo < Dr)
-          dqp[(int64_t)qi * dq_sl + 16 * dt + lo] = f2bf(acc_dq[sidx][dt][r]);
+          dqp[(int64_t)qi * dq_s.l + 16 * dt + lo] = f2bf(acc_dq[sidx][dt][r]);
     }
   }
 }
@@ -608,10 +591,8 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     const bf16* __restrict__ dO, const float* __restrict__ lse, bf16* __restrict__ dq,
     bf16* __restrict__ dk, bf16* __restrict__ dv, int Lq, int Lk, float scale, int H,
-    int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-    int64_t v_sb, int64_t v_sh, int64_t v_sl, int64_t do_sb, int64_t do_sh, int64_t do_sl,
-    int64_t dq_sb, int64_t dq_sh, int64_t dq_sl, int64_t dk_sb, int64_t dk_sh,
-    int64_t dk_sl, int64_t dv_sb, int64_t dv_sh, int64_t dv_sl) {
+    hstride q_s, hstride k_s, hstride v_s, hstride do_s, hstride dq_s, hstride dk_s,
+    hstride dv_s) {
   constexpr int D = 64;
   constexpr int LP = 96;         // image rows (three 32-row blocks)
   constexpr int TP = 88;         // tile pitch
@@ -629,29 +610,28 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
   const int lane = threadIdx.x % WAVE;
   const int lo = lane & 15, hi = lane >> 4;
   const int64_t bh = blockIdx.x;
-  const int64_t b = bh / H, h = bh % H;
-  const bf16* qp = q + b * q_sb + h * q_sh;
-  const bf16* kp = k + b * k_sb + h * k_sh;
-  const bf16* vp = v + b * v_sb + h * v_sh;
-  const bf16* dop = dO + b * do_sb + h * do_sh;
-  bf16* dqp = dq + b * dq_sb + h * dq_sh;
-  bf16* dkp = dk + b * dk_sb + h * dk_sh;
-  bf16* dvp = dv + b * dv_sb + h * dv_sh;
+  const bf16* qp = head_ptr(q, q_s, bh, H);
+  const bf16* kp = head_ptr(k, k_s, bh, H);
+  const bf16* vp = head_ptr(v, v_s, bh, H);
+  const bf16* dop = head_ptr(dO, do_s, bh, H);
+  bf16* dqp = head_ptr(dq, dq_s, bh, H);
+  bf16* dkp = head_ptr(dk, dk_s, bh, H);
+  bf16* dvp = head_ptr(dv, dv_s, bh, H);
 
   // zero the tiles + pad once (masked entries are never written)
   for (int i = threadIdx.x; i < (3 * TILE + 8) / 8; i += 320)
-    *reinterpret_cast<bf16x8_t*>(PT + i * 8) = bf16x8_t{};
+    *reinterpret_cast<bf16x8*>(PT + i * 8) = bf16x8{};
   auto stage = [&](short* img, const bf16* src, int64_t sl, int rows) {
     for (int idx = (int)threadIdx.x; idx < IMG / 8; idx += 320) {
       const int row = idx >> 3, d8 = (idx & 7) * 8;
-      bf16x8_t vv{};
-      if (row < rows) vv = *reinterpret_cast<const bf16x8_t*>(src + (int64_t)row * sl + d8);
-      *reinterpret_cast<bf16x8_t*>(img + boff<D>(row, d8)) = vv;
+      bf16x8 vv{};
+      if (row < rows) vv = *reinterpret_cast<const bf16x8*>(src + (int64_t)row * sl + d8);
+      *reinterpret_cast<bf16x8*>(img + boff<D>(row, d8)) = vv;
     }
   };
-  stage(imgA, kp, k_sl, Lk);
-  stage(imgQ, qp, q_sl, Lq);
-  stage(imgD, dop, do_sl, Lq);
+  stage(imgA, kp, k_s.l, Lk);
+  stage(imgQ, qp, q_s.l, Lq);
+  stage(imgD, dop, do_s.l, Lq);
   const int nq = (Lq + 15) / 16;
   const int nkt = (Lk + 15) / 16;
   __syncthreads();
@@ -661,30 +641,30 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
     const int qs = wave;
     const int q0 = 16 * qs;
     const int ktmax = CAUSAL ? min(nkt, qs + 1) : nkt;
-    bf16x8_t kfr[5][2], vfr[5][2];
+    bf16x8 kfr[5][2], vfr[5][2];
 #pragma unroll
     for (int kt = 0; kt < 5; ++kt) {
       const int key = 16 * kt + lo;
       const bool ok = kt < ktmax && key < Lk;
 #pragma unroll
       for (int sj = 0; sj < 2; ++sj) {
-        kfr[kt][sj] = ok ? *reinterpret_cast<const bf16x8_t*>(
-                               kp + (int64_t)key * k_sl + 32 * sj + hi * 8)
-                         : bf16x8_t{};
-        vfr[kt][sj] = ok ? *reinterpret_cast<const bf16x8_t*>(
-                               vp + (int64_t)key * v_sl + 32 * sj + hi * 8)
-                         : bf16x8_t{};
+        kfr[kt][sj] = ok ? *reinterpret_cast<const bf16x8*>(
+                               kp + (int64_t)key * k_s.l + 32 * sj + hi * 8)
+                         : bf16x8{};
+        vfr[kt][sj] = ok ? *reinterpret_cast<const bf16x8*>(
+                               vp + (int64_t)key * v_s.l + 32 * sj + hi * 8)
+                         : bf16x8{};
       }
     }
     const int qrow = min(q0 + lo, Lq - 1);
-    const bf16x8_t qb0 = *reinterpret_cast<const bf16x8_t*>(qp + (int64_t)qrow * q_sl + hi * 8);
-    const bf16x8_t qb1 =
-        *reinterpret_cast<const bf16x8_t*>(qp + (int64_t)qrow * q_sl + 32 + hi * 8);
-    const bf16x8_t db0 =
-        *reinterpret_cast<const bf16x8_t*>(dop + (int64_t)qrow * do_sl + hi * 8);
-    const bf16x8_t db1 =
-        *reinterpret_cast<const bf16x8_t*>(dop + (int64_t)qrow * do_sl + 32 + hi * 8);
-    f32x4_t sc[5] = {}, dpc[5] = {};
+    const bf16x8 qb0 = *reinterpret_cast<const bf16x8*>(qp + (int64_t)qrow * q_s.l + hi * 8);
+    const bf16x8 qb1 =
+        *reinterpret_cast<const bf16x8*>(qp + (int64_t)qrow * q_s.l + 32 + hi * 8);
+    const bf16x8 db0 =
+        *reinterpret_cast<const bf16x8*>(dop + (int64_t)qrow * do_s.l + hi * 8);
+    const bf16x8 db1 =
+        *reinterpret_cast<const bf16x8*>(dop + (int64_t)qrow * do_s.l + 32 + hi * 8);
+    f32x4 sc[5] = {}, dpc[5] = {};
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kt = 0; kt < 5; ++kt) {
@@ -728,15 +708,14 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
       *reinterpret_cast<bf16x4*>(DSQ + q_idx * TP + 16 * kt + 4 * hi) = ds4;
     }
     // dQ strip = dS @ K (B = tr fragments of the K image)
-    f32x4_t adq[4] = {};
+    f32x4 adq[4] = {};
     const int smax = (16 * ktmax + 31) / 32;
 #pragma unroll
     for (int sb = 0; sb < 3; ++sb) {
       if (sb >= smax) continue;
-      bf16x8_t bfr[4];
+      bf16x8 bfr[4];
       tr_frag_x4((lds_cp)(const void*)(imgA + sb * 32 * D) + lane * 8, bfr);
-      const bf16x8_t pa =
-          *reinterpret_cast<const bf16x8_t*>(DSQ + (q0 + lo) * TP + 32 * sb + hi * 8);
+      const bf16x8 pa = row_frag(DSQ, q0 + lo, TP, sb, hi);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) adq[dt] = MFMA16(pa, bfr[dt], adq[dt]);
@@ -748,7 +727,7 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
       if (qr >= Lq) continue;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
-        dqp[(int64_t)qr * dq_sl + 16 * dt + lo] = f2bf(adq[dt][r]);
+        dqp[(int64_t)qr * dq_s.l + 16 * dt + lo] = f2bf(adq[dt][r]);
     }
   }
   __syncthreads();  // phase-1 tile writes visible
@@ -758,15 +737,13 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
     const int k0 = 16 * wave;
     const int smin = CAUSAL ? k0 / 32 : 0;
     const int nsq = (Lq + 31) / 32;
-    f32x4_t adk[4] = {}, adv[4] = {};
+    f32x4 adk[4] = {}, adv[4] = {};
     for (int sb = smin; sb < nsq; ++sb) {
-      bf16x8_t bq[4], bd[4];
+      bf16x8 bq[4], bd[4];
       tr_frag_x4((lds_cp)(const void*)(imgQ + sb * 32 * D) + lane * 8, bq);
       tr_frag_x4((lds_cp)(const void*)(imgD + sb * 32 * D) + lane * 8, bd);
-      const bf16x8_t ak =
-          *reinterpret_cast<const bf16x8_t*>(DST + (k0 + lo) * TP + 32 * sb + hi * 8);
-      const bf16x8_t av =
-          *reinterpret_cast<const bf16x8_t*>(PT + (k0 + lo) * TP + 32 * sb + hi * 8);
+      const bf16x8 ak = row_frag(DST, k0 + lo, TP, sb, hi);
+      const bf16x8 av = row_frag(PT, k0 + lo, TP, sb, hi);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
@@ -781,8 +758,8 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
       if (kr >= Lk) continue;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        dkp[(int64_t)kr * dk_sl + 16 * dt + lo] = f2bf(adk[dt][r]);
-        dvp[(int64_t)kr * dv_sl + 16 * dt + lo] = f2bf(adv[dt][r]);
+        dkp[(int64_t)kr * dk_s.l + 16 * dt + lo] = f2bf(adk[dt][r]);
+        dvp[(int64_t)kr * dv_s.l + 16 * dt + lo] = f2bf(adv[dt][r]);
       }
     }
   }
@@ -848,11 +825,8 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     const bf16* __restrict__ o, const bf16* __restrict__ dO, const float* __restrict__ lse,
     bf16* __restrict__ dq, bf16* __restrict__ dk, bf16* __restrict__ dv, int L, float scale,
-    int H, int64_t q_sb, int64_t q_sh, int64_t q_sl, int64_t k_sb, int64_t k_sh, int64_t k_sl,
-    int64_t v_sb, int64_t v_sh, int64_t v_sl, int64_t o_sb, int64_t o_sh, int64_t o_sl,
-    int64_t do_sb, int64_t do_sh, int64_t do_sl, int64_t dq_sb, int64_t dq_sh, int64_t dq_sl,
-    int64_t dk_sb, int64_t dk_sh, int64_t dk_sl, int64_t dv_sb, int64_t dv_sh,
-    int64_t dv_sl) {
+    int H, hstride q_s, hstride k_s, hstride v_s, hstride o_s, hstride do_s, hstride dq_s,
+    hstride dk_s, hstride dv_s) {
   constexpr int D = 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int LP = (L + 31) & ~31;  // image rows: whole 32-row blocks
@@ -869,26 +843,25 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
   const int lane = tid % WAVE;
   const int lo = lane & 15, hi = lane >> 4;
   const int64_t bh = blockIdx.x;
-  const int64_t b = bh / H, h = bh % H;
-  const bf16* qp = q + b * q_sb + h * q_sh;
-  const bf16* kp = k + b * k_sb + h * k_sh;
-  const bf16* vp = v + b * v_sb + h * v_sh;
-  const bf16* op = o + b * o_sb + h * o_sh;
-  const bf16* dop = dO + b * do_sb + h * do_sh;
+  const bf16* qp = head_ptr(q, q_s, bh, H);
+  const bf16* kp = head_ptr(k, k_s, bh, H);
+  const bf16* vp = head_ptr(v, v_s, bh, H);
+  const bf16* op = head_ptr(o, o_s, bh, H);
+  const bf16* dop = head_ptr(dO, do_s, bh, H);
   const int nblk = LP / 32;
 
   // ---- a strip's own Q/dO rows (phase-1 B-fragments) and its delta ---------
-  bf16x8_t qb[2], dob[2];
+  bf16x8 qb[2], dob[2];
   float dl;
   auto load_rows = [&](int s0) {
     const int srow = min(s0 + lo, L - 1);
     dl = 0.f;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      qb[s] = *reinterpret_cast<const bf16x8_t*>(qp + (int64_t)srow * q_sl + 32 * s + hi * 8);
-      dob[s] = *reinterpret_cast<const bf16x8_t*>(dop + (int64_t)srow * do_sl + 32 * s + hi * 8);
-      const bf16x8_t ov =
-          *reinterpret_cast<const bf16x8_t*>(op + (int64_t)srow * o_sl + 32 * s + hi * 8);
+      qb[s] = *reinterpret_cast<const bf16x8*>(qp + (int64_t)srow * q_s.l + 32 * s + hi * 8);
+      dob[s] = *reinterpret_cast<const bf16x8*>(dop + (int64_t)srow * do_s.l + 32 * s + hi * 8);
+      const bf16x8 ov =
+          *reinterpret_cast<const bf16x8*>(op + (int64_t)srow * o_s.l + 32 * s + hi * 8);
 #pragma unroll
       for (int j = 0; j < 8; ++j) dl += bfs2f(dob[s][j]) * bfs2f(ov[j]);
     }
@@ -903,12 +876,12 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
     const int idx = tid + it * nthr;
     const int row = idx >> 3, d8 = (idx & 7) * 8;
     const int rc = min(row, L - 1);
-    bf16x8_t kk = *reinterpret_cast<const bf16x8_t*>(kp + (int64_t)rc * k_sl + d8);
-    bf16x8_t vv = *reinterpret_cast<const bf16x8_t*>(vp + (int64_t)rc * v_sl + d8);
-    if (row >= L) kk = vv = bf16x8_t{};
+    bf16x8 kk = *reinterpret_cast<const bf16x8*>(kp + (int64_t)rc * k_s.l + d8);
+    bf16x8 vv = *reinterpret_cast<const bf16x8*>(vp + (int64_t)rc * v_s.l + d8);
+    if (row >= L) kk = vv = bf16x8{};
     const int off = noff(row, d8);
-    *reinterpret_cast<bf16x8_t*>(imgA + off) = kk;
-    *reinterpret_cast<bf16x8_t*>(imgB + off) = vv;
+    *reinterpret_cast<bf16x8*>(imgA + off) = kk;
+    *reinterpret_cast<bf16x8*>(imgB + off) = vv;
   }
   for (int i = tid; i < LP; i += nthr) {
     lse_s[i] = i < L ? lse[bh * L + i] : 0.f;
@@ -926,18 +899,18 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
     const float lse_q = lse_s[min(s0 + lo, L - 1)];
     const float dli = dl;
     if (hi == 0) dl_s[s0 + lo] = dli;
-    f32x4_t adq[4] = {};
+    f32x4 adq[4] = {};
     for (int kb = 0; kb < nblk; ++kb) {
-      f32x4_t sc[2] = {}, dpc[2] = {};
+      f32x4 sc[2] = {}, dpc[2] = {};
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         if (32 * kb + 16 * t >= L) continue;  // whole 16-key tile is padding (wave-uniform)
-        bf16x8_t ka[2], va[2];
+        bf16x8 ka[2], va[2];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           const int off = noff(32 * kb + 16 * t + lo, 32 * s + hi * 8);
-          ka[s] = *reinterpret_cast<const bf16x8_t*>(imgA + off);
-          va[s] = *reinterpret_cast<const bf16x8_t*>(imgB + off);
+          ka[s] = *reinterpret_cast<const bf16x8*>(imgA + off);
+          va[s] = *reinterpret_cast<const bf16x8*>(imgB + off);
         }
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -947,7 +920,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
         }
         __builtin_amdgcn_s_setprio(0);
       }
-      bf16x8_t dsa;
+      bf16x8 dsa;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
@@ -959,7 +932,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
           dsa[4 * t + r] = f2bfs(ds);
         }
       }
-      bf16x8_t bfr[4];
+      bf16x8 bfr[4];
       tr_frag_x4((lds_cp)(const void*)(imgA + kb * 32 * D) + lane * 8, bfr);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -968,7 +941,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
     }
     // adq holds dQ^T tiles: lane = query lo, d = 16dt + 4hi + r -> 8-byte stores
     if (sok) {
-      bf16* dqp = dq + b * dq_sb + h * dq_sh + (int64_t)(s0 + lo) * dq_sl + 4 * hi;
+      bf16* dqp = head_ptr(dq, dq_s, bh, H) + (int64_t)(s0 + lo) * dq_s.l + 4 * hi;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         bf16x4 pk;
@@ -980,27 +953,27 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
   }
 
   // ---- between the phases: Q/dO replace K/V in the two image slots --------
-  bf16x8_t qst[4], dst[4];
+  bf16x8 qst[4], dst[4];
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     const int idx = tid + it * nthr;
     const int row = idx >> 3, d8 = (idx & 7) * 8;
     const int rc = min(row, L - 1);
-    qst[it] = *reinterpret_cast<const bf16x8_t*>(qp + (int64_t)rc * q_sl + d8);
-    dst[it] = *reinterpret_cast<const bf16x8_t*>(dop + (int64_t)rc * do_sl + d8);
-    if (row >= L) qst[it] = dst[it] = bf16x8_t{};
+    qst[it] = *reinterpret_cast<const bf16x8*>(qp + (int64_t)rc * q_s.l + d8);
+    dst[it] = *reinterpret_cast<const bf16x8*>(dop + (int64_t)rc * do_s.l + d8);
+    if (row >= L) qst[it] = dst[it] = bf16x8{};
   }
   // own K/V rows of the two key strips as phase-2 B-fragments, taken from
   // the images before they are overwritten (image rows >= L are zero)
-  bf16x8_t kbf[2][2], vbf[2][2];
+  bf16x8 kbf[2][2], vbf[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int srow = min(16 * (wave + i * nw) + lo, LP - 1);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int off = noff(srow, 32 * s + hi * 8);
-      kbf[i][s] = *reinterpret_cast<const bf16x8_t*>(imgA + off);
-      vbf[i][s] = *reinterpret_cast<const bf16x8_t*>(imgB + off);
+      kbf[i][s] = *reinterpret_cast<const bf16x8*>(imgA + off);
+      vbf[i][s] = *reinterpret_cast<const bf16x8*>(imgB + off);
     }
   }
   __syncthreads();  // barrier 2: K/V images retired, every strip's delta in LDS
@@ -1008,8 +981,8 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
   for (int it = 0; it < 4; ++it) {
     const int idx = tid + it * nthr;
     const int off = noff(idx >> 3, (idx & 7) * 8);
-    *reinterpret_cast<bf16x8_t*>(imgA + off) = qst[it];
-    *reinterpret_cast<bf16x8_t*>(imgB + off) = dst[it];
+    *reinterpret_cast<bf16x8*>(imgA + off) = qst[it];
+    *reinterpret_cast<bf16x8*>(imgB + off) = dst[it];
   }
   __syncthreads();  // barrier 3: Q/dO images published
 
@@ -1019,18 +992,18 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
     const int s0 = 16 * (wave + i * nw);
     if (s0 >= L) continue;  // wave-uniform
     const bool sok = s0 + lo < L;
-    f32x4_t adk[4] = {}, adv[4] = {};
+    f32x4 adk[4] = {}, adv[4] = {};
     for (int qblk = 0; qblk < nblk; ++qblk) {
-      f32x4_t sc[2] = {}, dpc[2] = {};
+      f32x4 sc[2] = {}, dpc[2] = {};
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         if (32 * qblk + 16 * t >= L) continue;  // whole 16-query tile is padding
-        bf16x8_t qa[2], da[2];
+        bf16x8 qa[2], da[2];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           const int off = noff(32 * qblk + 16 * t + lo, 32 * s + hi * 8);
-          qa[s] = *reinterpret_cast<const bf16x8_t*>(imgA + off);
-          da[s] = *reinterpret_cast<const bf16x8_t*>(imgB + off);
+          qa[s] = *reinterpret_cast<const bf16x8*>(imgA + off);
+          da[s] = *reinterpret_cast<const bf16x8*>(imgB + off);
         }
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -1040,12 +1013,12 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
         }
         __builtin_amdgcn_s_setprio(0);
       }
-      bf16x8_t pa, dsa;
+      bf16x8 pa, dsa;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int qi0 = 32 * qblk + 16 * t + 4 * hi;
-        const f32x4_t ls4 = *reinterpret_cast<const f32x4_t*>(lse_s + qi0);
-        const f32x4_t dl4 = *reinterpret_cast<const f32x4_t*>(dl_s + qi0);
+        const f32x4 ls4 = *reinterpret_cast<const f32x4*>(lse_s + qi0);
+        const f32x4 dl4 = *reinterpret_cast<const f32x4*>(dl_s + qi0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const bool ok = sok && qi0 + r < L;
@@ -1055,7 +1028,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
           dsa[4 * t + r] = f2bfs(ds);
         }
       }
-      bf16x8_t bfr[4];  // one fragment set at a time (register budget)
+      bf16x8 bfr[4];  // one fragment set at a time (register budget)
       tr_frag_x4((lds_cp)(const void*)(imgB + qblk * 32 * D) + lane * 8, bfr);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -1069,8 +1042,8 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
     }
     // transposed tiles again: lane = key lo, d = 16dt + 4hi + r
     if (sok) {
-      bf16* dkp = dk + b * dk_sb + h * dk_sh + (int64_t)(s0 + lo) * dk_sl + 4 * hi;
-      bf16* dvp = dv + b * dv_sb + h * dv_sh + (int64_t)(s0 + lo) * dv_sl + 4 * hi;
+      bf16* dkp = head_ptr(dk, dk_s, bh, H) + (int64_t)(s0 + lo) * dk_s.l + 4 * hi;
+      bf16* dvp = head_ptr(dv, dv_s, bh, H) + (int64_t)(s0 + lo) * dv_s.l + 4 * hi;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         bf16x4 pk, pv;
@@ -1091,17 +1064,13 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
 void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o,
                     torch::Tensor dO, torch::Tensor lse, torch::Tensor dq, torch::Tensor dk,
                     torch::Tensor dv, bool causal, double scale, std::string path) {
-  // all tensors (B,H,L,64) views, innermost contiguous, arbitrary b/h/l strides
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(q.dim() == 4, "attn_bwd_fused: (B,H,L,D) expected");
+  // all tensors (B,H,L,D) views, innermost contiguous, arbitrary b/h/l strides
+  check_attn_args("attn_bwd_fused", {{"q", q}, {"o", o}, {"dO", dO}, {"dq", dq}},
+                  {{"k", k}, {"v", v}, {"dk", dk}, {"dv", dv}}, &lse);
   const int Dr = q.size(3);
-  TORCH_CHECK(Dr == 64 || Dr == 72 || Dr == 80 || Dr == 96 || Dr == 128,
-              "attn_bwd_fused: head_dim must be one of {64,72,80,96,128}, got ", Dr);
   const int DP = Dr <= 64 ? 64 : (Dr <= 96 ? 96 : 128);
   const int B = q.size(0), H = q.size(1), Lq = q.size(2), Lk = k.size(2);
-  for (auto* t : {&q, &k, &v, &o, &dO, &dq, &dk, &dv})
-    TORCH_CHECK(t->stride(3) == 1, "attn_bwd_fused: innermost dim must be contiguous");
-  TORCH_CHECK(lse.is_contiguous() && lse.scalar_type() == torch::kFloat32);
+  const unsigned BH = (unsigned)((int64_t)B * H);
   auto stream = at::hip::getCurrentHIPStream();
 
   // path: "auto" picks small (L <= 80) / resident (81..RES_LMAX) / tiled;
@@ -1122,56 +1091,31 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
               " Lq=", Lq, " Lk=", Lk, " causal=", causal, " aligned=", res_aligned);
   if (path != "tiled" && resident_ok) {
     // one wave per 32 rows (two 16-row strips each); two images + lse + delta
-    for (auto* t : {&q, &k, &v, &o, &dO, &dq, &dk, &dv})
-      TORCH_CHECK(t->size(0) == B && t->size(1) == H && t->size(2) == Lk && t->size(3) == 64,
-                  "attn_bwd_fused: resident path needs equal (B,H,L,64) shapes");
-    TORCH_CHECK(lse.numel() == (int64_t)B * H * Lk, "attn_bwd_fused: lse must be (B,H,L)");
     const int LP = (Lk + 31) & ~31;
     const size_t rshmem = (size_t)2 * LP * 64 * sizeof(short) + (size_t)2 * LP * sizeof(float);
     // the LDS limit is raised once, to the largest supported L
     constexpr size_t rshmem_max =
         (size_t)2 * RES_LMAX * 64 * sizeof(short) + (size_t)2 * RES_LMAX * sizeof(float);
     launch_lds<attn_bwd_resident_kernel>(
-                       dim3((unsigned)((int64_t)B * H)), dim3(LP / 32 * WAVE), rshmem, rshmem_max,
-                       stream,
-                       reinterpret_cast<const bf16*>(q.data_ptr()),
-                       reinterpret_cast<const bf16*>(k.data_ptr()),
-                       reinterpret_cast<const bf16*>(v.data_ptr()),
-                       reinterpret_cast<const bf16*>(o.data_ptr()),
-                       reinterpret_cast<const bf16*>(dO.data_ptr()), lse.data_ptr<float>(),
-                       reinterpret_cast<bf16*>(dq.data_ptr()),
-                       reinterpret_cast<bf16*>(dk.data_ptr()),
-                       reinterpret_cast<bf16*>(dv.data_ptr()), Lk, (float)scale, H,
-                       q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
-                       k.stride(2), v.stride(0), v.stride(1), v.stride(2), o.stride(0),
-                       o.stride(1), o.stride(2), dO.stride(0), dO.stride(1), dO.stride(2),
-                       dq.stride(0), dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1),
-                       dk.stride(2), dv.stride(0), dv.stride(1), dv.stride(2));
+        dim3(BH), dim3(LP / 32 * WAVE), rshmem, rshmem_max, stream, bf16_ptr(q), bf16_ptr(k),
+        bf16_ptr(v), bf16_ptr(o), bf16_ptr(dO), lse.data_ptr<float>(), bf16_ptr(dq),
+        bf16_ptr(dk), bf16_ptr(dv), Lk, (float)scale, H, hstrides(q), hstrides(k), hstrides(v),
+        hstrides(o), hstrides(dO), hstrides(dq), hstrides(dk), hstrides(dv));
     return;
   }
 
   // small-L fused path: one kernel, no delta buffer (Lq == Lk <= 80, D = 64)
   if (path != "tiled" && Dr == 64 && Lq == Lk && Lk <= 80) {
-    const dim3 sgrid((unsigned)((int64_t)B * H));
-    const size_t sshmem = (3 * 96 * 64 + 3 * 80 * 88 + 8) * sizeof(short);
-#define SBWD_ARGS                                                                          \
-                     reinterpret_cast<const bf16*>(q.data_ptr()),                          \
-                     reinterpret_cast<const bf16*>(k.data_ptr()),                          \
-                     reinterpret_cast<const bf16*>(v.data_ptr()),                          \
-                     reinterpret_cast<const bf16*>(dO.data_ptr()), lse.data_ptr<float>(),  \
-                     reinterpret_cast<bf16*>(dq.data_ptr()),                               \
-                     reinterpret_cast<bf16*>(dk.data_ptr()),                               \
-                     reinterpret_cast<bf16*>(dv.data_ptr()), Lq, Lk, (float)scale, H,      \
-                     q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),      \
-                     k.stride(2), v.stride(0), v.stride(1), v.stride(2), dO.stride(0),     \
-                     dO.stride(1), dO.stride(2), dq.stride(0), dq.stride(1), dq.stride(2), \
-                     dk.stride(0), dk.stride(1), dk.stride(2), dv.stride(0), dv.stride(1), \
-                     dv.stride(2)
-    if (causal)
-      launch_lds<attn_bwd_small_kernel<true>>(sgrid, dim3(320), sshmem, sshmem, stream, SBWD_ARGS);
-    else
-      launch_lds<attn_bwd_small_kernel<false>>(sgrid, dim3(320), sshmem, sshmem, stream, SBWD_ARGS);
-#undef SBWD_ARGS
+    const size_t shmem = (3 * 96 * 64 + 3 * 80 * 88 + 8) * sizeof(short);
+    with_flags(
+        [&](auto c) {
+          launch_lds<attn_bwd_small_kernel<decltype(c)::value>>(
+              dim3(BH), dim3(320), shmem, shmem, stream, bf16_ptr(q), bf16_ptr(k), bf16_ptr(v),
+              bf16_ptr(dO), lse.data_ptr<float>(), bf16_ptr(dq), bf16_ptr(dk), bf16_ptr(dv), Lq,
+              Lk, (float)scale, H, hstrides(q), hstrides(k), hstrides(v), hstrides(dO),
+              hstrides(dq), hstrides(dk), hstrides(dv));
+        },
+        causal);
     return;
   }
 
@@ -1180,11 +1124,8 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
   {
     const int64_t nrows = (int64_t)B * H * Lq;
     const dim3 grid((unsigned)std::min<int64_t>((nrows + 3) / 4, 4096));
-    hipLaunchKernelGGL(attn_d2_kernel, grid, dim3(256), 0, stream,
-                       reinterpret_cast<const bf16*>(dO.data_ptr()),
-                       reinterpret_cast<const bf16*>(o.data_ptr()), Dv.data_ptr<float>(), H, Lq,
-                       Dr, nrows, dO.stride(0), dO.stride(1), dO.stride(2),
-                       o.stride(0), o.stride(1), o.stride(2));
+    hipLaunchKernelGGL(attn_d2_kernel, grid, dim3(256), 0, stream, bf16_ptr(dO), bf16_ptr(o),
+                       Dv.data_ptr<float>(), H, Lq, Dr, nrows, hstrides(dO), hstrides(o));
   }
 
   const int pitch = DP + 8;
@@ -1192,74 +1133,24 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
       (2 * (2 * BLK * DP + 2 * BLK * pitch) + 4 * 16 * pitch) * sizeof(short);
   const size_t shmem_dq = (2 * (BLK * DP + 2 * BLK * pitch) + 4 * 16 * pitch) * sizeof(short);
   const int ntk = (Lk + BLK - 1) / BLK;
-  static const int nkv_env = [] {
-    const char* e = getenv("JIMM_AMD_ATTN_NKV");
-    return e ? atoi(e) : 0;
-  }();
-  // DP > 64: one tile per workgroup (register budget)
-  const int nkv = DP != 64 ? 1 : (nkv_env ? nkv_env : 2);
-  const int nqs = DP != 64 ? 1 : 2;
-  const dim3 grid_dkv((ntk + nkv - 1) / nkv, (unsigned)((int64_t)B * H));
   const int ntq = (Lq + BLK - 1) / BLK;
-  const dim3 grid_dq((ntq + nqs - 1) / nqs, (unsigned)((int64_t)B * H));
-
-#define DKV_ARGS                                                                             \
-                     reinterpret_cast<const bf16*>(q.data_ptr()),                            \
-                     reinterpret_cast<const bf16*>(k.data_ptr()),                            \
-                     reinterpret_cast<const bf16*>(v.data_ptr()),                            \
-                     reinterpret_cast<const bf16*>(dO.data_ptr()), lse.data_ptr<float>(),    \
-                     Dv.data_ptr<float>(), reinterpret_cast<bf16*>(dk.data_ptr()),           \
-                     reinterpret_cast<bf16*>(dv.data_ptr()), Lq, Lk, (float)scale, H, Dr,    \
-                     q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),        \
-                     k.stride(2), v.stride(0), v.stride(1), v.stride(2), dO.stride(0),       \
-                     dO.stride(1), dO.stride(2), dk.stride(0), dk.stride(1), dk.stride(2),   \
-                     dv.stride(0), dv.stride(1), dv.stride(2)
-#define DKV_LAUNCH(C)                                                                        \
-  do {                                                                                       \
-    if (DP == 128)                                                                           \
-      launch_lds<attn_bwd_dkv_kernel<C, 1, 128>>(grid_dkv, dim3(256), shmem_dkv, shmem_dkv,  \
-                                                 stream, DKV_ARGS);                          \
-    else if (DP == 96)                                                                       \
-      launch_lds<attn_bwd_dkv_kernel<C, 1, 96>>(grid_dkv, dim3(256), shmem_dkv, shmem_dkv,   \
-                                                stream, DKV_ARGS);                           \
-    else if (nkv == 1)                                                                       \
-      launch_lds<attn_bwd_dkv_kernel<C, 1, 64>>(grid_dkv, dim3(256), shmem_dkv, shmem_dkv,   \
-                                                stream, DKV_ARGS);                           \
-    else                                                                                     \
-      launch_lds<attn_bwd_dkv_kernel<C, 2, 64>>(grid_dkv, dim3(256), shmem_dkv, shmem_dkv,   \
-                                                stream, DKV_ARGS);                           \
-  } while (0)
-#define DQ_ARGS                                                                              \
-                     reinterpret_cast<const bf16*>(q.data_ptr()),                            \
-                     reinterpret_cast<const bf16*>(k.data_ptr()),                            \
-                     reinterpret_cast<const bf16*>(v.data_ptr()),                            \
-                     reinterpret_cast<const bf16*>(dO.data_ptr()), lse.data_ptr<float>(),    \
-                     Dv.data_ptr<float>(), reinterpret_cast<bf16*>(dq.data_ptr()),           \
-                     Lq, Lk, (float)scale, H, Dr, q.stride(0), q.stride(1), q.stride(2),     \
-                     k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1),        \
-                     v.stride(2), dO.stride(0), dO.stride(1), dO.stride(2),                  \
-                     dq.stride(0), dq.stride(1), dq.stride(2)
-#define DQ_LAUNCH(C)                                                                         \
-  do {                                                                                       \
-    if (DP == 128)                                                                           \
-      launch_lds<attn_bwd_dq_kernel<C, 1, 128>>(grid_dq, dim3(256), shmem_dq, shmem_dq,      \
-                                                stream, DQ_ARGS);                            \
-    else if (DP == 96)                                                                       \
-      launch_lds<attn_bwd_dq_kernel<C, 1, 96>>(grid_dq, dim3(256), shmem_dq, shmem_dq,       \
-                                               stream, DQ_ARGS);                             \
-    else                                                                                     \
-      launch_lds<attn_bwd_dq_kernel<C, 2, 64>>(grid_dq, dim3(256), shmem_dq, shmem_dq,       \
-                                               stream, DQ_ARGS);                             \
-  } while (0)
-  if (causal) {
-    DKV_LAUNCH(true);
-    DQ_LAUNCH(true);
-  } else {
-    DKV_LAUNCH(false);
-    DQ_LAUNCH(false);
-  }
-#undef DKV_LAUNCH
-#undef DQ_LAUNCH
-#undef DKV_ARGS
-#undef DQ_ARGS
+  const int tpw = tiles_per_wg(DP);
+  with_flags(
+      [&](auto c) {
+        with_int<64, 96, 128>(DP, "padded head dim", [&](auto dp) {
+          constexpr bool C = decltype(c)::value;
+          constexpr int P = decltype(dp)::value;
+          launch_lds<attn_bwd_dkv_kernel<C, P>>(
+              dim3((ntk + tpw - 1) / tpw, BH), dim3(256), shmem_dkv, shmem_dkv, stream,
+              bf16_ptr(q), bf16_ptr(k), bf16_ptr(v), bf16_ptr(dO), lse.data_ptr<float>(),
+              Dv.data_ptr<float>(), bf16_ptr(dk), bf16_ptr(dv), Lq, Lk, (float)scale, H, Dr,
+              hstrides(q), hstrides(k), hstrides(v), hstrides(dO), hstrides(dk), hstrides(dv));
+          launch_lds<attn_bwd_dq_kernel<C, P>>(
+              dim3((ntq + tpw - 1) / tpw, BH), dim3(256), shmem_dq, shmem_dq, stream,
+              bf16_ptr(q), bf16_ptr(k), bf16_ptr(v), bf16_ptr(dO), lse.data_ptr<float>(),
+              Dv.data_ptr<float>(), bf16_ptr(dq), Lq, Lk, (float)scale, H, Dr, hstrides(q),
+              hstrides(k), hstrides(v), hstrides(dO), hstrides(dq));
+        });
+      },
+      causal);
 }

@@ -106,6 +106,40 @@ __device__ __forceinline__ void tr_frag_x2(lds_cp base, bf16x8 (&out)[2]) {
   out[1] = __builtin_shufflevector(a1l, a1h, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+// The NT = DP/16 B-fragments (4, 6 or 8) of one 32-contraction step.
+template <int NT>
+__device__ __forceinline__ void tr_frags(lds_cp base, bf16x8 (&out)[NT]) {
+  static_assert(NT == 4 || NT == 6 || NT == 8, "head dims 64, 96, 128");
+  tr_frag_x4(base, *reinterpret_cast<bf16x8(*)[4]>(&out[0]));
+  if constexpr (NT == 6) tr_frag_x2(base + 4096, *reinterpret_cast<bf16x8(*)[2]>(&out[4]));
+  if constexpr (NT == 8) tr_frag_x4(base + 4096, *reinterpret_cast<bf16x8(*)[4]>(&out[4]));
+}
+
+// The A/B fragment of contraction step `step` (columns 32*step + 8*hi .. +8 of
+// one row) from a row-major LDS image with `pitch` shorts per row. step and hi
+// are two arguments so that they are added to the pointer one after the
+// other: handed over as one summed column, the forward kernels compile to
+// different address arithmetic (5 more v_add3_u32, another VGPR count).
+__device__ __forceinline__ bf16x8 row_frag(const short* img, int row, int pitch, int step,
+                                           int hi) {
+  return *reinterpret_cast<const bf16x8*>(img + row * pitch + 32 * step + hi * 8);
+}
+
+// ---- attention: (B,H,L,D) views ---------------------------------------------
+
+// Element strides of one (B,H,L,D) view whose innermost dim is contiguous.
+// Kernels take one per tensor, next to its pointer (the pointers stay
+// separate __restrict__ parameters).
+struct hstride {
+  int64_t b, h, l;
+};
+
+// Row 0 of head bh = b*H + h.
+template <typename T>
+__device__ __forceinline__ T* head_ptr(T* base, const hstride& s, int64_t bh, int H) {
+  return base + (bh / H) * s.b + (bh % H) * s.h;
+}
+
 // ---- fused GEMM epilogue ---------------------------------------------------
 
 // What a forward GEMM writes to Z beside Y: nothing, the pre-activation
@@ -177,30 +211,25 @@ __device__ __forceinline__ void gemm_epilogue(float vpre, int m, int n, int N, f
 // (elementwise.hip)
 int act_code(const std::string& act);
 
-// Run-time values -> template arguments. with_act calls f with a
-// std::integral_constant<int, ACT_*> (with_save likewise); with_flags calls f with one
-// std::true_type / std::false_type per bool, in order. Read them back with
-// decltype(c)::value.
-template <typename F>
-void with_act(int act, F&& f) {
-  switch (act) {
-    case ACT_NONE: return f(std::integral_constant<int, ACT_NONE>{});
-    case ACT_GELU: return f(std::integral_constant<int, ACT_GELU>{});
-    case ACT_GELU_TANH: return f(std::integral_constant<int, ACT_GELU_TANH>{});
-    case ACT_QUICKGELU: return f(std::integral_constant<int, ACT_QUICKGELU>{});
-  }
-  TORCH_CHECK(false, "bad activation code ", act);
+// Run-time values -> template arguments. with_int calls f with the
+// std::integral_constant<int, V> whose V equals v and throws "bad <what> <v>"
+// when none does; with_act (ACT_*) and with_save (SAVE_*) are the two fixed
+// lists. with_flags calls f with one std::true_type / std::false_type per
+// bool, in order. Read them back with decltype(c)::value.
+template <int... Vs, typename F>
+void with_int(int v, const char* what, F&& f) {
+  const bool found = ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  TORCH_CHECK(found, "bad ", what, " ", v);
 }
 
-// with_save calls f with a std::integral_constant<int, SAVE_*>.
+template <typename F>
+void with_act(int act, F&& f) {
+  with_int<ACT_NONE, ACT_GELU, ACT_GELU_TANH, ACT_QUICKGELU>(act, "activation code", f);
+}
+
 template <typename F>
 void with_save(int save, F&& f) {
-  switch (save) {
-    case SAVE_NONE: return f(std::integral_constant<int, SAVE_NONE>{});
-    case SAVE_PRE: return f(std::integral_constant<int, SAVE_PRE>{});
-    case SAVE_GRAD: return f(std::integral_constant<int, SAVE_GRAD>{});
-  }
-  TORCH_CHECK(false, "bad save mode ", save);
+  with_int<SAVE_NONE, SAVE_PRE, SAVE_GRAD>(save, "save mode", f);
 }
 
 template <typename F>
@@ -228,4 +257,56 @@ void launch_lds(dim3 grid, dim3 block, size_t shmem, size_t shmem_limit, hipStre
   }();
   (void)raised;
   hipLaunchKernelGGL(Kernel, grid, block, shmem, stream, args...);
+}
+
+// ---- host: attention arguments ----------------------------------------------
+
+inline hstride hstrides(const torch::Tensor& t) {
+  return {t.stride(0), t.stride(1), t.stride(2)};
+}
+
+inline bf16* bf16_ptr(const torch::Tensor& t) {
+  return reinterpret_cast<bf16*>(t.data_ptr());
+}
+
+struct named_tensor {
+  const char* name;
+  const torch::Tensor& t;
+};
+
+// Argument checks of attn_fwd and attn_bwd_fused. Every tensor is a CUDA
+// bf16 (B,H,L,D) view with a contiguous innermost dim and a supported head
+// dim; q_like (q first: q, o, dO, dq) share q's shape, k_like (k first: k, v,
+// dk, dv) share k's, and k agrees with q in B, H and D. lse, where given, is
+// contiguous fp32 with B*H*Lq elements.
+inline void check_attn_args(const char* op, std::initializer_list<named_tensor> q_like,
+                            std::initializer_list<named_tensor> k_like,
+                            const torch::Tensor* lse = nullptr) {
+  const torch::Tensor& q = q_like.begin()->t;
+  const torch::Tensor& k = k_like.begin()->t;
+  for (const auto* list : {&q_like, &k_like}) {
+    const torch::Tensor& first = list->begin()->t;
+    for (const named_tensor& n : *list) {
+      TORCH_CHECK(n.t.is_cuda(), op, ": ", n.name, " must be a CUDA tensor");
+      TORCH_CHECK(n.t.scalar_type() == torch::kBFloat16, op, ": ", n.name,
+                  " must be bf16, got ", n.t.scalar_type());
+      TORCH_CHECK(n.t.dim() == 4, op, ": ", n.name, " must be (B,H,L,D), got ", n.t.dim(),
+                  " dims");
+      TORCH_CHECK(n.t.stride(3) == 1, op, ": innermost dim of ", n.name,
+                  " must be contiguous");
+      TORCH_CHECK(n.t.sizes() == first.sizes(), op, ": ", n.name, " has shape ", n.t.sizes(),
+                  ", expected ", list->begin()->name, "'s ", first.sizes());
+    }
+  }
+  const int64_t D = q.size(3);
+  TORCH_CHECK(D == 64 || D == 72 || D == 80 || D == 96 || D == 128, op,
+              ": head_dim must be one of {64,72,80,96,128}, got ", D);
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(1) == q.size(1) && k.size(3) == D, op,
+              ": k has shape ", k.sizes(), ", expected q's B, H and D ", q.sizes());
+  if (lse) {
+    TORCH_CHECK(lse->is_cuda() && lse->is_contiguous() &&
+                    lse->scalar_type() == torch::kFloat32 &&
+                    lse->numel() == q.size(0) * q.size(1) * q.size(2),
+                op, ": lse must be contiguous fp32 (B,H,Lq)");
+  }
 }

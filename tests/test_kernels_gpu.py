@@ -189,7 +189,8 @@ def test_attn_fwd_head_dims(D, causal):
 
 
 @pytest.mark.parametrize("D", [72, 80, 96, 128])
-def test_attn_bwd_head_dims(D):
+@pytest.mark.parametrize("causal", [False, True])
+def test_attn_bwd_head_dims(D, causal):
     torch.manual_seed(1)
     from jimm_amd import ops
 
@@ -198,12 +199,12 @@ def test_attn_bwd_head_dims(D):
     k = torch.randn(B, H, L, D, device=dev()).bfloat16().requires_grad_(True)
     v = torch.randn(B, H, L, D, device=dev()).bfloat16().requires_grad_(True)
     do = torch.randn(B, H, L, D, device=dev()).bfloat16()
-    out = ops.attention(q, k, v)
+    out = ops.attention(q, k, v, causal=causal)
     out.backward(do)
     qr = q.detach().float().requires_grad_(True)
     kr = k.detach().float().requires_grad_(True)
     vr = v.detach().float().requires_grad_(True)
-    _attn_ref(qr, kr, vr, False, 1.0 / math.sqrt(D)).backward(do.float())
+    _attn_ref(qr, kr, vr, causal, 1.0 / math.sqrt(D)).backward(do.float())
     assert rel_err(q.grad, qr.grad) < 5e-2
     assert rel_err(k.grad, kr.grad) < 5e-2
     assert rel_err(v.grad, vr.grad) < 5e-2
