@@ -38,3 +38,13 @@ for B, H, L, causal, tag in [
                for p in ("tiled", "resident")}
         print(f"{'':18s}         bwd tiled {2.5*tf_fwd/t_p['tiled']:6.1f} TF/s ({t_p['tiled']*1e3:6.3f} ms)  "
               f"resident {2.5*tf_fwd/t_p['resident']:6.1f} TF/s ({t_p['resident']*1e3:6.3f} ms)", flush=True)
+
+# resident domain of the forward: the two paths side by side
+for L in (96, 128, 197, 224, 256):
+    B, H = 256, 12
+    q = torch.randn(B, H, L, 64, device=dev).bfloat16()
+    k = torch.randn_like(q); v = torch.randn_like(q)
+    tf_fwd = 4 * B * H * L * L * 64 / 1e12
+    t_p = {p: bench(lambda p=p: ext.attn_fwd(q, k, v, False, 0.125, p)) for p in ("tiled", "resident")}
+    print(f"fwd bs256 L={L:4d}: tiled {tf_fwd/t_p['tiled']:6.1f} TF/s ({t_p['tiled']*1e3:6.3f} ms)  "
+          f"resident {tf_fwd/t_p['resident']:6.1f} TF/s ({t_p['resident']*1e3:6.3f} ms)", flush=True)

@@ -16,6 +16,10 @@
 //     re-shape from the S^T C-layout into the PV A-fragment layout;
 //   * online softmax with running (m, l) per q row; lse = m + log(l)
 //     saved for the backward (recompute) pass.
+// Two single-launch kernels take over where a whole (b, h) fits one
+// workgroup: attn_fwd_small_kernel (Lq == Lk <= 80) and
+// attn_fwd_resident_kernel (81 <= Lq == Lk <= 256, non-causal, ViT-B L=197);
+// both D = 64, see their header comments and the dispatch in attn_fwd.
 //
 // MFMA: v_mfma_f32_16x16x32_bf16. Fragment layouts (verified on hardware by
 // csrc/probe.hip + tests/test_kernels_gpu.py::test_mfma_probe):
@@ -455,10 +459,181 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Resident forward (Lq == Lk = L, 81 <= L <= 256, D = 64, non-causal; the
+// domain of attn_bwd_resident_kernel, whose phase 1 this is without dP and
+// delta). One workgroup per (b, h) with NBLK = ceil(L/32) waves; wave w owns
+// the 16-query strips w and w + NBLK. K and V are staged ONCE into two
+// natural-order block images (noff, mfma.h) with zero rows at and above L,
+// and nothing else lives in LDS: 57 344 B at L = 197, 65 536 B at L = 256,
+// so two workgroups share a CU and one loads or stores while the other
+// computes. The tiled kernel at L = 197 runs two workgroups per head that
+// both stage all of K and V, pads 197 rows to 256 and 197 keys to 256 with a
+// barrier every 64, sends P through an LDS tile and rescales O per kv tile.
+// Per strip:
+//   S^T = K.Q^T with ds_read_b128 A-fragments of the K image and the strip's
+//     Q rows in registers as B-fragments. ALL of the strip's scores stay in
+//     registers (2*NBLK tiles, 64 VGPRs at NBLK = 8; NBLK is a template
+//     argument so every index is a compile-time constant), so the softmax is
+//     one max, one exp pass and no rescale. Query = lane lo: the statistics
+//     are in-lane over (tile, r) plus __shfl_xor 16 and 32. (An online
+//     softmax over a run-time block loop was built too and measured 10-28 %
+//     slower at every L: profiles/attn_fwd_resident_NOTES.md.)
+//   Only the last 32-key block can hold keys >= L; they are masked to -inf
+//   by key index (a zero image row scores 0, not -inf). Padded query rows
+//   take m = +inf, so their P is exact 0 too.
+//   O^T += V^T.P^T: the tr_frag_x4 fragment of the V image is the A operand
+//     and the bf16 P fragment built from two accumulator tiles the B operand
+//     (see the backward kernel's header for the slot permutation), so the
+//     accumulators hold transposed tiles: lane = query lo, d = 16dt + 4hi + r.
+//     1/l is in-lane and the strip is stored as four 8-byte writes.
+// exp runs as v_exp_f32 on scores pre-multiplied by scale*log2(e); lse is
+// converted back to natural units.
+// Every global load is clamped to row L-1 and every store guarded by
+// row < L. The one barrier and every tr read are outside divergent control
+// flow (the strip skip is wave-uniform), so EXEC is all ones at each
+// ds_read_b64_tr_b16.
+// ---------------------------------------------------------------------------
+
+template <int NBLK>
+__global__ __launch_bounds__(512, 4) void attn_fwd_resident_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
+    bf16* __restrict__ o, float* __restrict__ lse, int L, float scale, int H, hstride q_s,
+    hstride k_s, hstride v_s, hstride o_s) {
+  constexpr int D = 64;
+  constexpr int LP = 32 * NBLK;  // image rows: whole 32-row blocks
+  constexpr int IMG = LP * D;
+  constexpr int NTHR = 64 * NBLK;  // the image has exactly 4 16-B chunks per thread
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  short* imgK = reinterpret_cast<short*>(smem);
+  short* imgV = imgK + IMG;
+
+  const int tid = threadIdx.x;
+  const int wave = tid / WAVE;
+  const int lane = tid % WAVE;
+  const int lo = lane & 15, hi = lane >> 4;
+  const int64_t bh = blockIdx.x;
+  const bf16* qp = head_ptr(q, q_s, bh, H);
+  const bf16* kp = head_ptr(k, k_s, bh, H);
+  const bf16* vp = head_ptr(v, v_s, bh, H);
+
+  // ---- both strips' Q rows (B-fragments), in flight under the staging -------
+  bf16x8 qb[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int srow = min(16 * (wave + i * NBLK) + lo, L - 1);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      qb[i][s] = *reinterpret_cast<const bf16x8*>(qp + (int64_t)srow * q_s.l + 32 * s + hi * 8);
+  }
+
+  // ---- stage K, V ------------------------------------------------------------
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int idx = tid + it * NTHR;
+    const int row = idx >> 3, d8 = (idx & 7) * 8;
+    const int rc = min(row, L - 1);
+    bf16x8 kk = *reinterpret_cast<const bf16x8*>(kp + (int64_t)rc * k_s.l + d8);
+    bf16x8 vv = *reinterpret_cast<const bf16x8*>(vp + (int64_t)rc * v_s.l + d8);
+    if (row >= L) kk = vv = bf16x8{};
+    const int off = noff(row, d8);
+    *reinterpret_cast<bf16x8*>(imgK + off) = kk;
+    *reinterpret_cast<bf16x8*>(imgV + off) = vv;
+  }
+  __syncthreads();
+
+  const float c = scale * 1.44269504088896340736f;  // scores in log2 units
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int s0 = 16 * (wave + i * NBLK);
+    if (s0 >= L) continue;  // wave-uniform
+    const bool sok = s0 + lo < L;
+
+    // ---- S^T = K . Q^T, all 2*NBLK key tiles ---------------------------------
+    f32x4 sc[NBLK][2];
+#pragma unroll
+    for (int kb = 0; kb < NBLK; ++kb) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        sc[kb][t] = f32x4{};
+        // whole 16-key tile is padding (wave-uniform; masked below)
+        if (kb == NBLK - 1 && 32 * kb + 16 * t >= L) continue;
+        bf16x8 ka[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+          ka[s] = *reinterpret_cast<const bf16x8*>(
+              imgK + noff(32 * kb + 16 * t + lo, 32 * s + hi * 8));
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) sc[kb][t] = MFMA16(ka[s], qb[i][s], sc[kb][t]);
+        __builtin_amdgcn_s_setprio(0);
+      }
+    }
+
+    // ---- row max over every key (query = lane lo) ----------------------------
+    float m = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < NBLK; ++kb) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float x = sc[kb][t][r] * c;
+          if (kb == NBLK - 1 && 32 * kb + 16 * t + 4 * hi + r >= L) x = -INFINITY;
+          sc[kb][t][r] = x;
+          m = fmaxf(m, x);
+        }
+      }
+    }
+    m = fmaxf(m, __shfl_xor(m, 16, WAVE));
+    m = fmaxf(m, __shfl_xor(m, 32, WAVE));
+    const float msub = sok ? m : INFINITY;  // padded query rows: P = exp2(-inf) = 0
+
+    // ---- P = exp2(S - m) 32 keys at a time; O^T += V^T . P^T -----------------
+    float lsum = 0.f;
+    f32x4 acc[4] = {};
+#pragma unroll
+    for (int kb = 0; kb < NBLK; ++kb) {
+      bf16x8 pf;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = __builtin_amdgcn_exp2f(sc[kb][t][r] - msub);
+          lsum += p;
+          pf[4 * t + r] = f2bfs(p);
+        }
+      }
+      bf16x8 vfr[4];
+      tr_frag_x4((lds_cp)(const void*)(imgV + kb * 32 * D) + lane * 8, vfr);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) acc[dt] = MFMA16(vfr[dt], pf, acc[dt]);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    lsum += __shfl_xor(lsum, 16, WAVE);
+    lsum += __shfl_xor(lsum, 32, WAVE);
+
+    // acc holds O^T tiles: lane = query lo, d = 16dt + 4hi + r -> 8-byte stores
+    if (sok) {
+      const float invl = 1.f / lsum;
+      bf16* op = head_ptr(o, o_s, bh, H) + (int64_t)(s0 + lo) * o_s.l + 4 * hi;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        bf16x4 pk;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pk[r] = f2bfs(acc[dt][r] * invl);
+        *reinterpret_cast<bf16x4*>(op + 16 * dt) = pk;
+      }
+      if (hi == 0) lse[bh * L + s0 + lo] = m * 0.69314718055994530942f + __logf(lsum);
+    }
+  }
+}
+
 }  // namespace
 
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                                    bool causal, double scale) {
+                                    bool causal, double scale, std::string path) {
   // q,k,v: (B,H,L,D) views whose innermost dim is contiguous — covers both
   // contiguous BHLD and the un-copied (B,L,H,D) / fused-qkv (B,L,3,H,D)
   // layouts.
@@ -466,12 +641,38 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
   const int Dr = q.size(3);
   const int DP = Dr <= 64 ? 64 : (Dr <= 96 ? 96 : 128);
   const int B = q.size(0), H = q.size(1), Lq = q.size(2), Lk = k.size(2);
+  // path: "auto" picks small (L <= 80) / resident (81..RES_LMAX) / tiled;
+  // "tiled" is auto without the resident kernel; "resident" fails outside
+  // its domain
+  TORCH_CHECK(path == "auto" || path == "tiled" || path == "resident",
+              "attn_fwd: path must be auto, tiled or resident, got ", path);
+  const bool aligned = res_aligned({&q, &k, &v});  // o is allocated below, aligned
+  const bool resident_ok = Dr == 64 && Lq == Lk && !causal && Lk >= RES_LMIN &&
+                           Lk <= RES_LMAX && aligned;
+  TORCH_CHECK(path != "resident" || resident_ok,
+              "attn_fwd: path=resident needs D == 64, Lq == Lk, non-causal, ", RES_LMIN,
+              " <= L <= ", RES_LMAX, " and 16-byte aligned rows; got D=", Dr, " Lq=", Lq,
+              " Lk=", Lk, " causal=", causal, " aligned=", aligned);
   // O written in (B,L,H,D) memory order so the model's (B,L,H*D) reshape is
   // a free view (no permute copy)
   auto o = torch::empty({B, Lq, H, Dr}, q.options()).permute({0, 2, 1, 3});
   auto lse = torch::empty({B, H, Lq}, q.options().dtype(torch::kFloat32));
   const unsigned BH = (unsigned)((int64_t)B * H);
   auto stream = at::hip::getCurrentHIPStream();
+  if (path != "tiled" && resident_ok) {
+    // one wave per 32 rows (two 16-row strips each); K and V images only.
+    // The LDS limit is raised once, to the largest supported L.
+    const int nblk = (Lk + 31) / 32;
+    const size_t rshmem = (size_t)2 * nblk * 32 * 64 * sizeof(short);
+    constexpr size_t rshmem_max = (size_t)2 * RES_LMAX * 64 * sizeof(short);
+    with_int<3, 4, 5, 6, 7, 8>(nblk, "resident block count", [&](auto nb) {
+      launch_lds<attn_fwd_resident_kernel<decltype(nb)::value>>(
+          dim3(BH), dim3(nblk * WAVE), rshmem, rshmem_max, stream, bf16_ptr(q), bf16_ptr(k),
+          bf16_ptr(v), bf16_ptr(o), lse.data_ptr<float>(), Lk, (float)scale, H, hstrides(q),
+          hstrides(k), hstrides(v), hstrides(o));
+    });
+    return {o, lse};
+  }
   with_flags(
       [&](auto c) {
         constexpr bool C = decltype(c)::value;

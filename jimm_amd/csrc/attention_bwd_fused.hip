@@ -812,14 +812,9 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
 // Q/dO images to phase 2. All three barriers and every tr read are outside
 // divergent control flow (the branches around them are wave-uniform), so
 // EXEC is all ones at each ds_read_b64_tr_b16.
+// RES_LMIN, RES_LMAX and the image layout noff are in mfma.h (shared with the
+// resident forward, attention.hip).
 // ---------------------------------------------------------------------------
-
-constexpr int RES_LMIN = 81;
-constexpr int RES_LMAX = 256;
-
-__device__ __forceinline__ int noff(int row, int d) {
-  return (row >> 5) * 2048 + (d >> 4) * 512 + (row & 31) * 16 + (d & 15);
-}
 
 __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
@@ -1077,18 +1072,13 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
   // "tiled" forces d2 + dkv + dq; "resident" fails outside its domain
   TORCH_CHECK(path == "auto" || path == "tiled" || path == "resident",
               "attn_bwd_fused: path must be auto, tiled or resident, got ", path);
-  // the resident kernel stores 8 bytes at a time: rows must be 16-byte aligned
-  // (true of every view the model passes; anything else stays on the tiled path)
-  bool res_aligned = true;
-  for (auto* t : {&q, &k, &v, &o, &dO, &dq, &dk, &dv})
-    res_aligned = res_aligned && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0 &&
-                  t->stride(0) % 8 == 0 && t->stride(1) % 8 == 0 && t->stride(2) % 8 == 0;
+  const bool aligned = res_aligned({&q, &k, &v, &o, &dO, &dq, &dk, &dv});
   const bool resident_ok = Dr == 64 && Lq == Lk && !causal && Lk >= RES_LMIN &&
-                           Lk <= RES_LMAX && res_aligned;
+                           Lk <= RES_LMAX && aligned;
   TORCH_CHECK(path != "resident" || resident_ok,
               "attn_bwd_fused: path=resident needs D == 64, Lq == Lk, non-causal, ",
               RES_LMIN, " <= L <= ", RES_LMAX, " and 16-byte aligned rows; got D=", Dr,
-              " Lq=", Lq, " Lk=", Lk, " causal=", causal, " aligned=", res_aligned);
+              " Lq=", Lq, " Lk=", Lk, " causal=", causal, " aligned=", aligned);
   if (path != "tiled" && resident_ok) {
     // one wave per 32 rows (two 16-row strips each); two images + lse + delta
     const int LP = (Lk + 31) & ~31;

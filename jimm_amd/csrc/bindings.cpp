@@ -35,7 +35,7 @@ std::vector<torch::Tensor> adam_prepare(std::vector<torch::Tensor> ps,
 void adam_apply(torch::Tensor desc, int64_t nchunks, torch::Tensor lr_dev,
                 torch::Tensor step_dev, double b1, double b2, double eps, double wd);
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                                    bool causal, double scale);
+                                    bool causal, double scale, std::string path);
 void attn_bwd_p(torch::Tensor s, torch::Tensor lse, bool causal, double scale);
 torch::Tensor attn_d(torch::Tensor dO, torch::Tensor O);
 void attn_ds(torch::Tensor dp, torch::Tensor p, torch::Tensor D, double scale);
@@ -87,7 +87,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step", &adam_step, "fused multi-tensor Adam (K14)");
   m.def("adam_prepare", &adam_prepare, "build device chunk descriptors once (K14)");
   m.def("adam_apply", &adam_apply, "graph-capturable fused Adam update (K14)");
-  m.def("attn_fwd", &attn_fwd, "flash attention forward, head_dim 64 (K5)");
+  m.def("attn_fwd", &attn_fwd,
+        "flash attention forward (K5); path: auto | tiled | resident",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),
+        py::arg("path") = "auto");
   m.def("attn_bwd_p", &attn_bwd_p, "attention bwd: S -> P in place (K15)");
   m.def("attn_d", &attn_d, "attention bwd: rowsum(dO*O) (K15)");
   m.def("attn_ds", &attn_ds, "attention bwd: dP -> dS in place (K15)");

@@ -140,6 +140,21 @@ __device__ __forceinline__ T* head_ptr(T* base, const hstride& s, int64_t bh, in
   return base + (bh / H) * s.b + (bh % H) * s.h;
 }
 
+// ---- attention: resident kernels (one workgroup per head) --------------------
+
+// Domain of the resident forward and backward: D = 64, Lq == Lk = L,
+// non-causal, RES_LMIN <= L <= RES_LMAX, res_aligned views (host section).
+constexpr int RES_LMIN = 81;
+constexpr int RES_LMAX = 256;
+
+// Natural-order block image of a [rows][64 d] operand: 32-row blocks of four
+// 16-d sub-blocks, rows 32 B apart inside a sub-block. Unlike boff<> the 8
+// row-quads keep their order, which is what lets two accumulator tiles serve
+// as the next MFMA's fragment (attention_bwd_fused.hip, resident kernel).
+__device__ __forceinline__ int noff(int row, int d) {
+  return (row >> 5) * 2048 + (d >> 4) * 512 + (row & 31) * 16 + (d & 15);
+}
+
 // ---- fused GEMM epilogue ---------------------------------------------------
 
 // What a forward GEMM writes to Z beside Y: nothing, the pre-activation
@@ -267,6 +282,17 @@ inline hstride hstrides(const torch::Tensor& t) {
 
 inline bf16* bf16_ptr(const torch::Tensor& t) {
   return reinterpret_cast<bf16*>(t.data_ptr());
+}
+
+// The resident attention kernels load 16 and store 8 bytes at a time: every
+// base must be 16-byte aligned and every stride a multiple of 8 elements
+// (true of every view the model passes; anything else stays on a tiled path).
+inline bool res_aligned(std::initializer_list<const torch::Tensor*> ts) {
+  bool ok = true;
+  for (const torch::Tensor* t : ts)
+    ok = ok && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0 && t->stride(0) % 8 == 0 &&
+         t->stride(1) % 8 == 0 && t->stride(2) % 8 == 0;
+  return ok;
 }
 
 struct named_tensor {
