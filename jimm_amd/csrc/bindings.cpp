@@ -61,11 +61,17 @@ torch::Tensor gemm_nt_8p_gradact(torch::Tensor dy, torch::Tensor wt, torch::Tens
 torch::Tensor tr16_probe(torch::Tensor src, int64_t mode);
 std::vector<torch::Tensor> linear_fwd(torch::Tensor x, torch::Tensor w,
                                       c10::optional<torch::Tensor> bias, std::string act,
-                                      c10::optional<torch::Tensor> residual, bool save_z);
+                                      c10::optional<torch::Tensor> residual, bool save_z,
+                                      double p, c10::optional<torch::Tensor> rng,
+                                      int64_t site);
 std::vector<torch::Tensor> linear_fwd_actgrad(torch::Tensor x, torch::Tensor w,
                                               c10::optional<torch::Tensor> bias,
                                               std::string act,
-                                              c10::optional<torch::Tensor> residual);
+                                              c10::optional<torch::Tensor> residual,
+                                              double p, c10::optional<torch::Tensor> rng,
+                                              int64_t site);
+torch::Tensor dropout_fwd(torch::Tensor x, double p, c10::optional<torch::Tensor> rng,
+                          int64_t site);
 torch::Tensor gemm_nt_8p_gradmul(torch::Tensor dy, torch::Tensor wt, torch::Tensor g);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -117,11 +123,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xent_rows_fwd", &xent_rows_fwd, "fused softmax-CE forward (K13)");
   m.def("xent_rows_bwd", &xent_rows_bwd, "fused softmax-CE backward (K13)");
   m.def("sigmoid_loss_ew", &sigmoid_loss_ew, "SigLIP sigmoid loss + dLogits (K13)");
-  m.def("linear_fwd", &linear_fwd, "MFMA GEMM + fused epilogue (K4/K6/K7/K8)");
+  m.def("linear_fwd", &linear_fwd,
+        "MFMA GEMM + fused epilogue (K4/K6/K7/K8); p > 0 fuses dropout at `site`",
+        py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("act"), py::arg("residual"),
+        py::arg("save_z"), py::arg("p") = 0.0, py::arg("rng") = py::none(),
+        py::arg("site") = 0);
   m.def("linear_fwd_actgrad", &linear_fwd_actgrad,
         "linear_fwd that returns (y, fp16 act'(pre)) instead of the pre-activation",
         py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("act"),
-        py::arg("residual") = py::none());
+        py::arg("residual") = py::none(), py::arg("p") = 0.0, py::arg("rng") = py::none(),
+        py::arg("site") = 0);
+  m.def("dropout_fwd", &dropout_fwd,
+        "counter-based dropout of an (M, N) tensor under the device {seed, step} pair rng",
+        py::arg("x"), py::arg("p"), py::arg("rng"), py::arg("site") = 0);
   m.def("gemm_nt_8p_gradmul", &gemm_nt_8p_gradmul,
         "dX GEMM times a saved fp16 activation derivative");
 }

@@ -5,6 +5,8 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
+#include <cmath>
+
 #define WAVE 64  // CDNA wavefront width (not 32!)
 
 #define HIP_CHECK(expr)                                                     \
@@ -158,6 +160,82 @@ __device__ __forceinline__ unsigned short cvt2_e4m3(float a, float b) {
 
 __device__ __forceinline__ unsigned char cvt_e4m3(float a) {
   return (unsigned char)(cvt2_e4m3(a, 0.f) & 0xff);
+}
+
+// ---- counter-based dropout (ops/philox_dropout.py holds the definition) -----------
+// Philox4x32, 10 rounds, standard constants: 20 v_mul_lo/v_mul_hi pairs and
+// 20 xors per call, no state. Element (m, n) of a rows x cols tensor reads
+// counter {m >> 1, (n >> 6) * 16 + (n & 15), site, step}, key {seed lo, seed
+// hi}, word (n >> 4) & 3, low half for even m, high half for odd m; so one
+// call serves rows {2i, 2i+1} x columns {c, c+16, c+32, c+48} of a 64-group.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
+                                              unsigned k0, unsigned k1, unsigned (&out)[4]) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+// What a dropout kernel needs beside its data: the device {seed, step} pair
+// (read on the device, so a captured graph never bakes the values in), the
+// site, the keep threshold t = round(p * 65536) and s = 65536 / (65536 - t).
+struct drop_args {
+  const long long* rng;
+  unsigned site;
+  unsigned thresh;
+  float scale;
+};
+
+// {seed, step} as the key and the last counter word (wave-uniform; load once
+// per kernel, outside the element loops).
+struct drop_key {
+  unsigned k0, k1, step;
+};
+
+__device__ __forceinline__ drop_key load_drop_key(const drop_args& d) {
+  const unsigned long long seed = (unsigned long long)d.rng[0];
+  return {(unsigned)seed, (unsigned)(seed >> 32), (unsigned)d.rng[1]};
+}
+
+// The eight 0-or-s multipliers of one Philox call: dm[half][word] for rows
+// {2 * mpair + half} and columns {64 * (cgroup >> 4) + 16 * word + (cgroup & 15)}.
+__device__ __forceinline__ void drop_mults(const drop_args& d, const drop_key& k, unsigned mpair,
+                                           unsigned cgroup, float (&dm)[2][4]) {
+  unsigned w[4];
+  philox4x32_10(mpair, cgroup, d.site, k.step, k.k0, k.k1, w);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    dm[0][i] = (w[i] & 0xffffu) >= d.thresh ? d.scale : 0.f;
+    dm[1][i] = (w[i] >> 16) >= d.thresh ? d.scale : 0.f;
+  }
+}
+
+// Host: t = round(p * 65536), halves up (ops/philox_dropout.py dropout_threshold).
+inline unsigned drop_threshold(double p) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout probability must be in [0, 1), got ", p);
+  const double t = std::floor(p * 65536.0 + 0.5);
+  return t > 65535.0 ? 65535u : (unsigned)t;
+}
+
+// Host: kernel arguments of a dropout with threshold t > 0 on x's device.
+inline drop_args make_drop_args(unsigned t, const c10::optional<torch::Tensor>& rng,
+                                int64_t site, const torch::Tensor& x) {
+  TORCH_CHECK(rng.has_value(), "dropout with p > 0 needs the {seed, step} tensor");
+  TORCH_CHECK(rng->is_cuda() && rng->device() == x.device() &&
+                  rng->scalar_type() == torch::kInt64 && rng->numel() == 2 &&
+                  rng->is_contiguous(),
+              "dropout rng must be a contiguous int64[2] tensor on the input's device");
+  TORCH_CHECK(site >= 0 && site <= 0xffffffffLL, "dropout site must fit 32 bits, got ", site);
+  return {reinterpret_cast<const long long*>(rng->data_ptr()), (unsigned)site, t,
+          (float)(65536.0 / (65536.0 - (double)t))};
 }
 
 // ---- vectorized load/store helpers (G13: hipcc does not auto-vectorize

@@ -3,6 +3,7 @@
 //                     y = act(z) [+ residual]; acts: gelu / gelu_tanh /
 //                     quickgelu (K7 epilogue; transformer.py:92-103)
 //   * act_bwd       — dz = dy * act'(z)
+//   * dropout_fwd   — counter-based dropout (Philox per 8 outputs), fwd = bwd
 //   * im2col/col2im — K1 patch-embed gather for kernel==stride convs
 //                     (common/vit.py:153-165,228-230): pure permute-gather,
 //                     coalesced on the cols side.
@@ -231,6 +232,54 @@ __global__ void embed_pos_kernel(const int64_t* __restrict__ ids, const T* __res
   }
 }
 
+// Counter-based dropout (definition: common.h / ops/philox_dropout.py): y = x * s
+// where kept, 0 where dropped; the backward is the same kernel on dy. A
+// thread owns rows {2i, 2i+1} x columns 4j..4j+3 of each of the four 16-column
+// words of one 64-column group: 4 Philox calls for 32 elements (one call per
+// 8 outputs, every word and half used), moved as eight 8-byte accesses.
+// VEC needs N % 4 == 0 (rows stay 8-byte aligned and a 4-column chunk is all
+// in or all out of a ragged last group); otherwise elements go one by one.
+template <typename T, bool VEC>
+__global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t M, int N,
+                               drop_args d) {
+  const drop_key key = load_drop_key(d);
+  const int G = (N + 63) / 64;
+  const int64_t total = ((M + 1) / 2) * G * 4;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (int64_t)gridDim.x * blockDim.x) {
+    const int j = (int)(idx & 3);
+    const int g = (int)((idx >> 2) % G);
+    const int64_t mp = idx / (4 * (int64_t)G);
+    float dm[4][2][4];  // [column q][row half][word]
+#pragma unroll
+    for (int q = 0; q < 4; ++q) drop_mults(d, key, (unsigned)mp, g * 16 + 4 * j + q, dm[q]);
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int64_t row = 2 * mp + half;
+      if (row >= M) break;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const int n = 64 * g + 16 * w + 4 * j;
+        if (VEC) {
+          if (n >= N) break;
+          float v[4];
+          vload_f32<4>(x + row * N + n, v);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) v[q] = dm[q][half][w] == 0.f ? 0.f : v[q] * dm[q][half][w];
+          vstore_f32<4>(y + row * N + n, v);
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            if (n + q >= N) break;
+            const float m = dm[q][half][w];
+            y[row * N + n + q] = (T)(m == 0.f ? 0.f : (float)x[row * N + n + q] * m);
+          }
+        }
+      }
+    }
+  }
+}
+
 template <typename T>
 void launch_bias_act(torch::Tensor& z, const c10::optional<torch::Tensor>& bias,
                      const c10::optional<torch::Tensor>& res, torch::Tensor& y, int M,
@@ -324,6 +373,42 @@ torch::Tensor act_bwd(torch::Tensor dy, torch::Tensor z, std::string act) {
     TORCH_CHECK(false, "act_bwd: unsupported dtype");
   }
   return dz;
+}
+
+// y = dropout(x) at `site` under the device {seed, step} pair `rng`; x is
+// (M, N) bf16 or fp32. p that rounds to a zero threshold returns x.
+torch::Tensor dropout_fwd(torch::Tensor x, double p, c10::optional<torch::Tensor> rng,
+                          int64_t site) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2, "dropout_fwd: x must be a "
+              "contiguous CUDA (M, N) tensor");
+  const unsigned t = drop_threshold(p);
+  if (t == 0) return x;
+  const drop_args d = make_drop_args(t, rng, site, x);
+  auto y = torch::empty_like(x);
+  const int64_t M = x.size(0);
+  const int N = x.size(1);
+  if (x.numel() == 0) return y;
+  const int64_t n = ((M + 1) / 2) * ((N + 63) / 64) * 4;
+  const int block = 256;
+  const int grid = (int)std::min<int64_t>((n + block - 1) / block, 8 * kMaxGrid);
+  auto stream = at::hip::getCurrentHIPStream();
+  auto launch = [&](auto t_tag) {
+    using T = decltype(t_tag);
+    const T* xp = reinterpret_cast<const T*>(x.data_ptr());
+    T* yp = reinterpret_cast<T*>(y.data_ptr());
+    const bool aligned = reinterpret_cast<uintptr_t>(xp) % 16 == 0 &&
+                         reinterpret_cast<uintptr_t>(yp) % 16 == 0;
+    if (N % 4 == 0 && aligned)
+      hipLaunchKernelGGL((dropout_kernel<T, true>), dim3(grid), dim3(block), 0, stream, xp, yp,
+                         M, N, d);
+    else
+      hipLaunchKernelGGL((dropout_kernel<T, false>), dim3(grid), dim3(block), 0, stream, xp, yp,
+                         M, N, d);
+  };
+  if (x.scalar_type() == torch::kBFloat16) launch(bf16{});
+  else if (x.scalar_type() == torch::kFloat32) launch(0.f);
+  else TORCH_CHECK(false, "dropout_fwd: unsupported dtype ", x.scalar_type());
+  return y;
 }
 
 torch::Tensor colsum(torch::Tensor dz) {

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(
 bool gemm8p_supported(int64_t M, int64_t N, int64_t K);
 void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias,
                 std::string act, c10::optional<torch::Tensor> residual, torch::Tensor y,
-                int save, c10::optional<torch::Tensor> z);
+                int save, c10::optional<torch::Tensor> z, const drop_args* drop);
 
 bool gemm_supported(int64_t M, int64_t N, int64_t K, std::string dtype) {
   if (dtype != "torch.bfloat16") return false;
@@ -263,14 +263,26 @@ namespace {
 // y = act(x @ w^T + bias) [+ residual] and, per `save` (SAVE_*), nothing,
 // the bf16 pre-activation or the fp16 activation derivative as the second
 // tensor (undefined = None in Python for SAVE_NONE).
+// p > 0: dropout at `site` under the device {seed, step} pair `rng`, fused
+// into the 8-phase kernel's epilogue (gemm_nt_8p names the two forms); a
+// shape that kernel does not take is an error, raised before any launch.
 std::vector<torch::Tensor> linear_fwd_impl(torch::Tensor x, torch::Tensor w,
                                            c10::optional<torch::Tensor> bias, std::string act,
-                                           c10::optional<torch::Tensor> residual, int save) {
+                                           c10::optional<torch::Tensor> residual, int save,
+                                           double p, c10::optional<torch::Tensor> rng,
+                                           int64_t site) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && w.is_contiguous());
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2);
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K && K % BK == 0);
+  const unsigned thresh = drop_threshold(p);
+  drop_args drop = {};
+  if (thresh > 0) {
+    TORCH_CHECK(gemm8p_supported(M, N, K), "linear_fwd: dropout is fused into the 8-phase "
+                "kernel only, which does not take M=", M, " N=", N, " K=", K);
+    drop = make_drop_args(thresh, rng, site, x);
+  }
   TORCH_CHECK(save != SAVE_GRAD || !act.empty(),
               "saving the activation derivative needs an activation");
   if (residual)
@@ -293,7 +305,7 @@ std::vector<torch::Tensor> linear_fwd_impl(torch::Tensor x, torch::Tensor w,
   if (save != SAVE_NONE) zopt = z;
 
   if (gemm8p_supported(M, N, K)) {
-    gemm_nt_8p(x, w, b, act, residual, y, save, zopt);
+    gemm_nt_8p(x, w, b, act, residual, y, save, zopt, thresh > 0 ? &drop : nullptr);
     return {y, z};
   }
 
@@ -336,16 +348,23 @@ std::vector<torch::Tensor> linear_fwd_impl(torch::Tensor x, torch::Tensor w,
 
 std::vector<torch::Tensor> linear_fwd(torch::Tensor x, torch::Tensor w,
                                       c10::optional<torch::Tensor> bias, std::string act,
-                                      c10::optional<torch::Tensor> residual, bool save_z) {
-  return linear_fwd_impl(x, w, bias, act, residual, save_z ? SAVE_PRE : SAVE_NONE);
+                                      c10::optional<torch::Tensor> residual, bool save_z,
+                                      double p, c10::optional<torch::Tensor> rng,
+                                      int64_t site) {
+  return linear_fwd_impl(x, w, bias, act, residual, save_z ? SAVE_PRE : SAVE_NONE, p, rng,
+                         site);
 }
 
 // The forward of an activated linear that saves g = act'(x @ w^T + bias) as
 // fp16 in place of the pre-activation: returns {y, g}, y bitwise what
-// linear_fwd returns. gemm_nt_8p_gradmul consumes g.
+// linear_fwd returns. gemm_nt_8p_gradmul consumes g. With p > 0 both carry the
+// dropout that follows the activation: y = act(pre)*m*s, g = act'(pre)*m*s,
+// so that backward needs nothing beyond the same gradmul.
 std::vector<torch::Tensor> linear_fwd_actgrad(torch::Tensor x, torch::Tensor w,
                                               c10::optional<torch::Tensor> bias,
                                               std::string act,
-                                              c10::optional<torch::Tensor> residual) {
-  return linear_fwd_impl(x, w, bias, act, residual, SAVE_GRAD);
+                                              c10::optional<torch::Tensor> residual,
+                                              double p, c10::optional<torch::Tensor> rng,
+                                              int64_t site) {
+  return linear_fwd_impl(x, w, bias, act, residual, SAVE_GRAD, p, rng, site);
 }

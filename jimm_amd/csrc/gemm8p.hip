@@ -45,7 +45,9 @@
 // pre-activation or the fp16 activation derivative (SAVE_*, mfma.h); the dX
 // variants multiply by act'(z) recomputed from a saved z (GRADM_ACT) or by a
 // saved fp16 derivative (GRADM_MUL: one load, convert and multiply per
-// element, no activation code).
+// element, no activation code). DROP fuses counter-based dropout (common.h)
+// into the two forward forms the MLP has: a lane's 16 elements of a fragment
+// are the 4 words x 2 halves of two Philox calls, made in the epilogue loops.
 // M may be ragged (MGUARD clamps staging rows and predicates stores);
 // N%256==0, K%64==0, K>=128 required (gemm8p_supported).
 
@@ -89,13 +91,13 @@ __device__ __forceinline__ int frag_off(int row, int chunk) {
 }
 
 template <int ACT, bool HAS_BIAS, bool HAS_RES, int SAVE, bool MGUARD, int GRADM = GRADM_NONE,
-          bool FP8O = false>
+          bool FP8O = false, bool DROP = false>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
     const bf16* __restrict__ X, const bf16* __restrict__ W, const void* __restrict__ bias,
     int bias_bf16, const bf16* __restrict__ res, bf16* __restrict__ Y, bf16* __restrict__ Z,
     int M, int N, int K, unsigned char* __restrict__ Y8 = nullptr,
     const float* __restrict__ scale8 = nullptr,
-    unsigned int* __restrict__ amax_bits = nullptr) {
+    unsigned int* __restrict__ amax_bits = nullptr, drop_args drop = {}) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // A images: [buf 0..1][half 0..1] at (buf*2+half)*16 KiB;
   // B images: [slot 0..2][half 0..1] at 64 KiB + (slot*2+half)*16 KiB.
@@ -232,19 +234,52 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
     for (int ni = 0; ni < 4; ++ni)
       bv[ni] = load_bias(bias, n0 + wn * 64 + 16 * ni + lo, bias_bf16);
   }
+  if constexpr (DROP) {
+    // A lane's 16 elements of a fragment are rows hi*4 + {0..3} x columns
+    // 16*ni + lo of the wave's 64-column group: the 4 words x 2 halves of two
+    // Philox calls (one per row pair), every word used, nothing crosses lanes.
+    const drop_key dkey = load_drop_key(drop);
+    const unsigned cgroup = ((n0 >> 6) + wn) * 16 + lo;
 #pragma unroll
-  for (int pr = 0; pr < 2; ++pr) {
+    for (int pr = 0; pr < 2; ++pr) {
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
+      for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + pr * 128 + wm * 64 + 16 * mi + hi * 4 + r;
-        if (MGUARD && m >= M) continue;
+        for (int rp = 0; rp < 2; ++rp) {
+          const int mb = m0 + pr * 128 + wm * 64 + 16 * mi + hi * 4 + 2 * rp;
+          if (MGUARD && mb >= M) continue;
+          float dm[2][4];
+          drop_mults(drop, dkey, (unsigned)mb >> 1, cgroup, dm);
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          const int n = n0 + wn * 64 + 16 * ni + lo;
-          gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE, GRADM, FP8O>(
-              acc[pr][mi][ni][r], m, n, N, bv[ni], res, Y, Z, Y8, rs8, &tmax);
+          for (int rr = 0; rr < 2; ++rr) {
+            const int m = mb + rr;
+            if (MGUARD && m >= M) continue;
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) {
+              const int n = n0 + wn * 64 + 16 * ni + lo;
+              gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE, GRADM, FP8O, true>(
+                  acc[pr][mi][ni][2 * rp + rr], m, n, N, bv[ni], res, Y, Z, Y8, rs8, &tmax,
+                  dm[rr][ni]);
+            }
+          }
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int pr = 0; pr < 2; ++pr) {
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = m0 + pr * 128 + wm * 64 + 16 * mi + hi * 4 + r;
+          if (MGUARD && m >= M) continue;
+#pragma unroll
+          for (int ni = 0; ni < 4; ++ni) {
+            const int n = n0 + wn * 64 + 16 * ni + lo;
+            gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE, GRADM, FP8O>(
+                acc[pr][mi][ni][r], m, n, N, bv[ni], res, Y, Z, Y8, rs8, &tmax);
+          }
         }
       }
     }
@@ -268,14 +303,16 @@ namespace {
 template <auto Kernel>
 void launch_8p(const torch::Tensor& x, const torch::Tensor& w, const void* biasp, int bias_bf16,
                const bf16* resp, torch::Tensor& y, bf16* zp, unsigned char* y8p = nullptr,
-               const float* scale8p = nullptr, unsigned int* amaxp = nullptr) {
+               const float* scale8p = nullptr, unsigned int* amaxp = nullptr,
+               drop_args drop = {}) {
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   constexpr size_t shmem = 10 * HALF_BYTES;
   const int mt = (M + BM - 1) / BM;
   launch_lds<Kernel>(dim3(mt * (N / BN)), dim3(NTHREADS), shmem, shmem,
                      at::hip::getCurrentHIPStream(), reinterpret_cast<const bf16*>(x.data_ptr()),
                      reinterpret_cast<const bf16*>(w.data_ptr()), biasp, bias_bf16, resp,
-                     reinterpret_cast<bf16*>(y.data_ptr()), zp, M, N, K, y8p, scale8p, amaxp);
+                     reinterpret_cast<bf16*>(y.data_ptr()), zp, M, N, K, y8p, scale8p, amaxp,
+                     drop);
 }
 
 // dz = (dy @ wt^T as NT on pre-transposed wt [in_f, out_f]) * act'(z) —
@@ -351,12 +388,18 @@ torch::Tensor gemm_nt_8p_gradmul(torch::Tensor dy, torch::Tensor wt, torch::Tens
 }
 
 // bias: fp32 or bf16, read as it is. save: SAVE_*; z receives what it names.
+// drop (nullptr = none): dropout fused into the epilogue, for the two forms
+// the MLP has: fc1 (activation, bias, no residual, SAVE_GRAD) and fc2 (no
+// activation, bias, residual, SAVE_NONE).
 void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias,
                 std::string act, c10::optional<torch::Tensor> residual, torch::Tensor y,
-                int save, c10::optional<torch::Tensor> z) {
+                int save, c10::optional<torch::Tensor> z, const drop_args* drop) {
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(gemm8p_supported(M, N, K));
   TORCH_CHECK((save != SAVE_NONE) == z.has_value());
+  // s * act' must stay an fp16: act' <= 1.13
+  TORCH_CHECK(!drop || save != SAVE_GRAD || drop->scale * 1.25f < 65504.f,
+              "dropout epilogue: the scaled derivative overflows fp16 at this p");
   const bf16* resp = residual ? reinterpret_cast<const bf16*>(residual->data_ptr()) : nullptr;
   const void* biasp = bias ? bias->data_ptr() : nullptr;
   const int bias_bf16 = bias && bias->scalar_type() == torch::kBFloat16;
@@ -367,8 +410,20 @@ void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> b
       with_flags(
           [&](auto hb, auto hr, auto mg) {
             constexpr int A = decltype(act_c)::value, S = decltype(save_c)::value;
+            constexpr bool HB = decltype(hb)::value, HR = decltype(hr)::value;
+            constexpr bool fc1 = A != ACT_NONE && HB && !HR && S == SAVE_GRAD;
+            constexpr bool fc2 = A == ACT_NONE && HB && HR && S == SAVE_NONE;
             if constexpr (S == SAVE_GRAD && A == ACT_NONE) {
               TORCH_CHECK(false, "saving the activation derivative needs an activation");
+            } else if (drop) {
+              if constexpr (fc1 || fc2) {
+                launch_8p<gemm_nt_8p_kernel<A, true, HR, S, decltype(mg)::value, GRADM_NONE,
+                                            false, true>>(x, w, biasp, bias_bf16, resp, y, zp,
+                                                          nullptr, nullptr, nullptr, *drop);
+              } else {
+                TORCH_CHECK(false, "dropout epilogue: only act + bias + saved derivative (fc1) "
+                                   "or bias + residual (fc2)");
+              }
             } else {
               launch_8p<gemm_nt_8p_kernel<A, decltype(hb)::value, decltype(hr)::value, S,
                                           decltype(mg)::value>>(x, w, biasp, bias_bf16, resp, y,

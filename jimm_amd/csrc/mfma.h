@@ -189,13 +189,21 @@ __device__ __forceinline__ float load_bias(const void* bias, int n, int bias_bf1
 //       copy (consumed by the fp8 dX GEMM); the caller reduces tmax.
 // Y is the same bits in every SAVE mode: act_fwd is act_fwd_grad with the
 // derivative dropped.
+// DROP (forward only): dm is this element's dropout multiplier, 0 or
+// s = 1 / keep rate (common.h); it scales act(vpre) before the residual is
+// added and the saved derivative, so the backward of the dropout that follows
+// an activation is already in Z:
+//   Y = dm * bf16(act(vpre)) with an activation, dm * vpre (+ res) without;
+//   Z = fp16 dm * act'(vpre) (SAVE_GRAD)
 template <int ACT, bool HAS_BIAS, bool HAS_RES, int SAVE, int GRADM = GRADM_NONE,
-          bool FP8O = false>
+          bool FP8O = false, bool DROP = false>
 __device__ __forceinline__ void gemm_epilogue(float vpre, int m, int n, int N, float bias_n,
                                               const bf16* res, bf16* Y, bf16* Z,
                                               unsigned char* Y8 = nullptr, float rs8 = 1.f,
-                                              float* tmax = nullptr) {
+                                              float* tmax = nullptr, float dm = 1.f) {
   static_assert(SAVE != SAVE_GRAD || ACT != ACT_NONE, "SAVE_GRAD needs an activation");
+  static_assert(!DROP || (GRADM == GRADM_NONE && SAVE != SAVE_PRE && !FP8O),
+                "dropout epilogue: forward GEMMs that save nothing or the derivative");
   if (HAS_BIAS) vpre += bias_n;
   if (SAVE == SAVE_PRE) Z[(int64_t)m * N + n] = f2bf(vpre);
   float vy;
@@ -207,9 +215,17 @@ __device__ __forceinline__ void gemm_epilogue(float vpre, int m, int n, int N, f
     if (SAVE == SAVE_GRAD) {
       float g;
       vy = act_fwd_grad(vpre, ACT, &g);
+      if (DROP) g *= dm;
       reinterpret_cast<__half*>(Z)[(int64_t)m * N + n] = __float2half(g);
     } else {
       vy = act_fwd(vpre, ACT);
+    }
+    if (DROP) {
+      // an activated output is rounded to bf16 BEFORE it is scaled: Y is then
+      // bit for bit dropout_fwd of the p = 0 output (one rounding away from
+      // s times it, not two), and the fused and the unfused block agree
+      if (ACT != ACT_NONE) vy = bf2f(f2bf(vy));
+      vy *= dm;
     }
     if (HAS_RES) vy += bf2f(res[(int64_t)m * N + n]);
   }

@@ -55,7 +55,10 @@ class EncoderBlock(nn.Module):
         self.proj = nn.Linear(hidden_size, hidden_size, bias=True)
         self.fc1 = nn.Linear(hidden_size, mlp_dim, bias=True)
         self.fc2 = nn.Linear(mlp_dim, hidden_size, bias=True)
-        self.dropout = nn.Dropout(dropout_rate)
+        self.dropout = nn.Dropout(dropout_rate)  # holds p; ops.dropout does the work
+        # dropout sites of this block: site0 after the activation, site0 + 1
+        # after fc2 (an Encoder numbers its layers 2 * layer_index)
+        self.site0 = 0
 
     def _forward_tp(self, x: torch.Tensor) -> torch.Tensor:
         """Tensor-parallel path (parallel/tp.py): local heads + local MLP
@@ -79,18 +82,31 @@ class EncoderBlock(nn.Module):
         part = ops.linear(h, self.fc2.weight)
         return reduce_from_tp(part, g) + self.fc2.bias + x
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, rng: torch.Tensor | None = None) -> torch.Tensor:
+        """rng: the ``{seed, step}`` snapshot of this forward pass
+        (``ops.next_dropout_rng``), handed down by the Encoder so that a
+        checkpoint recompute sees the same masks; a block called on its own
+        draws one. Only read in training mode with dropout_rate > 0."""
         if getattr(self, "_tp_group", None) is not None:
             return self._forward_tp(x)
         from jimm_amd.ops import block as fused
 
-        if fused.fused_block_enabled(x, self.dropout.p) and self.head_dim in (64, 72, 80, 96, 128):
+        # the ACTIVE dropout probability: eval of a dropout-built model is
+        # the dropout-free model, fused block included
+        p = self.dropout.p if self.training else 0.0
+        if p > 0 and rng is None:
+            rng = ops.next_dropout_rng(x.device)
+        if (
+            fused.fused_block_enabled(x, p, self.fc1.out_features)
+            and self.head_dim in (64, 72, 80, 96, 128)
+        ):
             import math
 
             return fused.encoder_block(
                 x, self.norm1, self.qkv, self.proj, self.norm2, self.fc1, self.fc2,
                 num_heads=self.num_heads, act=self.act, eps=self.eps,
                 causal=self.causal, scale=1.0 / math.sqrt(self.head_dim),
+                p=p, rng=rng, site0=self.site0,
             )
         B, L, H = x.shape
         h = ops.layer_norm(x, self.norm1.weight, self.norm1.bias, self.eps)
@@ -102,10 +118,10 @@ class EncoderBlock(nn.Module):
 
         h = ops.layer_norm(x, self.norm2.weight, self.norm2.bias, self.eps)
         h = ops.linear(h, self.fc1.weight, self.fc1.bias, act=self.act)
-        if self.dropout.p > 0:
-            h = self.dropout(h)
+        if p > 0:
+            h = ops.dropout(h, p, rng, self.site0)
             h = ops.linear(h, self.fc2.weight, self.fc2.bias)
-            return x + self.dropout(h)
+            return x + ops.dropout(h, p, rng, self.site0 + 1)
         # dropout inactive: residual add fused into the fc2 epilogue (K8)
         return ops.linear(h, self.fc2.weight, self.fc2.bias, residual=x)
 
@@ -141,8 +157,17 @@ class Encoder(nn.Module):
             )
             for _ in range(num_layers)
         )
+        self.dropout_rate = dropout_rate
+        for i, layer in enumerate(self.layers):
+            layer.site0 = 2 * i
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        # One {seed, step} snapshot per forward pass, shared by every block:
+        # a checkpointed block's recompute replays identical masks, and a
+        # second tower or a second forward draws the next step.
+        rng = None
+        if self.training and self.dropout_rate > 0:
+            rng = ops.next_dropout_rng(x.device)
         if getattr(self, "gradient_checkpointing", False) and torch.is_grad_enabled():
             from torch.utils.checkpoint import checkpoint
 
@@ -157,10 +182,10 @@ class Encoder(nn.Module):
             every = int(getattr(self, "checkpoint_every", 1) or 1)
             for i, layer in enumerate(self.layers):
                 if i % every == 0:
-                    x = checkpoint(layer, x, use_reentrant=False)
+                    x = checkpoint(layer, x, rng, use_reentrant=False)
                 else:
-                    x = layer(x)
+                    x = layer(x, rng)
             return x
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x, rng)
         return x

@@ -23,6 +23,10 @@ from torch import nn
 from jimm_amd import ops
 from jimm_amd.models.common.transformer import Encoder
 
+# Dropout site of the embeddings (after CLS concat + position add). Encoder
+# layers use sites 2 * layer_index and 2 * layer_index + 1, far below it.
+EMBED_DROPOUT_SITE = 1 << 30
+
 
 class MAPHead(nn.Module):
     """SigLIP Multihead-Attention-Pooling head.
@@ -143,7 +147,7 @@ class VisionTransformerBase(nn.Module):
             self.dropout = None
         else:
             self.ln_pre = None
-            self.dropout = nn.Dropout(dropout_rate)
+            self.dropout = nn.Dropout(dropout_rate)  # holds p; ops.dropout does the work
 
         self.encoder = Encoder(
             num_layers,
@@ -168,8 +172,8 @@ class VisionTransformerBase(nn.Module):
         x = ops.add_cls_pos(x, self.cls_token, self.pos_embedding)
         if self.ln_pre is not None:
             x = ops.layer_norm(x, self.ln_pre.weight, self.ln_pre.bias, self.eps)
-        else:
-            x = self.dropout(x)
+        elif self.training and self.dropout.p > 0:
+            x = ops.dropout(x, self.dropout.p, ops.next_dropout_rng(x.device), EMBED_DROPOUT_SITE)
         x = self.encoder(x)
         x = ops.layer_norm(x, self.ln_post.weight, self.ln_post.bias, self.eps)
         if not pool or self.pooling == "NONE":

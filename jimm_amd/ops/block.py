@@ -11,8 +11,12 @@ residual / act-backward epilogues fused in; under ``set_fp8(True)`` (and
 past the M*H size gate) the forward GEMMs and fc1-dX run e4m3 with
 producer-fused quantization and per-block delayed scaling.
 
-Enabled on GPU when dropout == 0 (the composite path remains the reference
-and the dropout/CPU path). JIMM_AMD_FUSED_BLOCK=0 disables.
+Active dropout (training, p > 0) stays on this path where the bf16 HIP GEMMs
+take both MLP shapes: the fc1 and fc2 epilogues compute the counter-based
+masks (ops/philox_dropout.py) in registers, fc1 saves the masked derivative,
+and the backward regenerates the fc2-site mask on dy with one elementwise
+pass. Otherwise the composite path (the reference and the CPU path) runs
+with ops.dropout. JIMM_AMD_FUSED_BLOCK=0 disables.
 """
 
 from __future__ import annotations
@@ -22,7 +26,8 @@ import os
 import torch
 
 from jimm_amd.ops import _backend
-from jimm_amd.ops.hip_linear import _dw_db_gemm, _dx_gemm, _gemm_mode
+from jimm_amd.ops.hip_linear import _FP8_STATE, _dw_db_gemm, _dx_gemm, _gemm_mode
+from jimm_amd.ops.philox_dropout import dropout_threshold
 
 
 def _hip_gemms(M: int, H: int) -> bool:
@@ -82,13 +87,29 @@ def _mm_fp8q(y8: torch.Tensor, s: torch.Tensor, w: torch.Tensor,
     )
 
 
-def fused_block_enabled(x: torch.Tensor, dropout_p: float) -> bool:
+def _fused_dropout_ok(x: torch.Tensor, dropout_p: float, mlp_dim: int | None) -> bool:
+    """Active dropout stays on the fused block where both MLP GEMMs run the
+    8-phase kernel (its fc1 / fc2 epilogues compute the masks) and fc1 saves
+    the fp16 derivative, which then carries the activation-site mask to the
+    backward. p so close to 1 that s * act' leaves fp16 is not taken."""
+    if mlp_dim is None or _gemm_mode() != "hip" or not _act_save_g() or _FP8_STATE["enabled"]:
+        return False
+    if dropout_threshold(dropout_p) > 65000:
+        return False
+    M, H = x.numel() // x.shape[-1], x.shape[-1]
+    ext = _backend.ext()
+    return ext.gemm8p_supported(M, mlp_dim, H) and ext.gemm8p_supported(M, H, mlp_dim)
+
+
+def fused_block_enabled(x: torch.Tensor, dropout_p: float, mlp_dim: int | None = None) -> bool:
+    """dropout_p is the ACTIVE probability (0 in eval mode); with p > 0 the
+    caller passes the MLP width so the GEMM shapes can be checked."""
     return (
         x.is_cuda
-        and dropout_p == 0.0
         and x.dtype == torch.bfloat16
         and _backend.use_hip(x)
         and os.environ.get("JIMM_AMD_FUSED_BLOCK", "1") == "1"
+        and (dropout_threshold(dropout_p) == 0 or _fused_dropout_ok(x, dropout_p, mlp_dim))
     )
 
 
@@ -98,12 +119,19 @@ class EncoderBlockFn(torch.autograd.Function):
         ctx, x, ln1w, ln1b, wqkv, bqkv, wproj, bproj, ln2w, ln2b, w1, b1, w2, b2,
         scale8, amax8,
         num_heads: int, act: str, eps: float, causal: bool, scale: float,
+        p: float = 0.0, rng: torch.Tensor | None = None, site0: int = 0,
     ):
         ext = _backend.ext()
         B, L, H = x.shape
         x = x.contiguous()
         x2 = x.view(-1, H)
         hip = _hip_gemms(B * L, H)
+        # active dropout: site0 after the activation, site0 + 1 after fc2,
+        # both under the {seed, step} snapshot rng (fused_block_enabled has
+        # checked that the bf16 HIP save-g path below takes these shapes)
+        drop = dropout_threshold(p) > 0
+        if not drop:
+            p, rng = 0.0, None
 
         # Producer-fused fp8 (BASELINE config 5): LN / bias-act kernels emit
         # the e4m3 copy of their output alongside bf16 (one extra store, no
@@ -128,6 +156,8 @@ class EncoderBlockFn(torch.autograd.Function):
             and B * L * H > _FP8_MIN_MH
             and hasattr(torch, "_scaled_mm")
         )
+        if drop and (fp8 or not hip):
+            raise RuntimeError("fused block: dropout runs on the bf16 HIP GEMM path only")
         if fp8:
             amax8.zero_()
             h1, h1q, mean1, rstd1 = ext.layernorm_fwd_fp8(
@@ -171,11 +201,16 @@ class EncoderBlockFn(torch.autograd.Function):
             # z1 holds the fp16 derivative act'(pre) instead of the
             # pre-activation (nothing else reads z1)
             save_g = _act_save_g() and ext.gemm8p_supported(B * L, w1.shape[0], H)
+            if drop and not save_g:
+                raise RuntimeError("fused block: dropout needs the saved-derivative fc1 path")
             if save_g:
-                f, z1 = ext.linear_fwd_actgrad(h2.view(-1, H), w1, b1, act, None)
+                # with dropout f = act(z)*m*s and z1 = act'(z)*m*s: the mask
+                # of site0 reaches the backward inside the saved derivative
+                f, z1 = ext.linear_fwd_actgrad(h2.view(-1, H), w1, b1, act, None, p, rng, site0)
             else:
                 f, z1 = ext.linear_fwd(h2.view(-1, H), w1, b1, act, None, True)
-            y, _ = ext.linear_fwd(f, w2, b2, "", a, False)
+            # y = a + m*s*(f @ w2^T + b2) at site0 + 1
+            y, _ = ext.linear_fwd(f, w2, b2, "", a, False, p, rng, site0 + 1)
         else:
             a2 = torch.matmul(o2, wproj.t())
             a = ext.bias_act_fwd(a2, bproj, "", x2)              # + bias + residual (one pass)
@@ -186,9 +221,10 @@ class EncoderBlockFn(torch.autograd.Function):
             y2 = torch.matmul(f, w2.t())
             y = ext.bias_act_fwd(y2, b2, "", a)                  # + bias + residual
         ctx.save_for_backward(x, ln1w, wqkv, wproj, ln2w, w1, w2,
-                              h1, qkv, o, lse, a, mean1, rstd1, mean2, rstd2, h2, z1, f)
+                              h1, qkv, o, lse, a, mean1, rstd1, mean2, rstd2, h2, z1, f, rng)
         ctx.dims = (B, L, H, num_heads)
         ctx.meta = (act, causal, scale)
+        ctx.drop = (p, site0)
         ctx.fp8_state = (scale8, amax8) if fp8 else None
         return y.view(B, L, H)
 
@@ -196,10 +232,15 @@ class EncoderBlockFn(torch.autograd.Function):
     def backward(ctx, dy):
         ext = _backend.ext()
         (x, ln1w, wqkv, wproj, ln2w, w1, w2,
-         h1, qkv, o, lse, a, mean1, rstd1, mean2, rstd2, h2, z1, f) = ctx.saved_tensors
+         h1, qkv, o, lse, a, mean1, rstd1, mean2, rstd2, h2, z1, f, rng) = ctx.saved_tensors
         B, L, H, nh = ctx.dims
         act, causal, scale = ctx.meta
+        p, site0 = ctx.drop
         dy2 = dy.contiguous().view(-1, H)
+        # dropout after fc2: its backward regenerates the mask on dy. dyd
+        # feeds fc2's dX, dW and db; the residual branch (the LN2 addend
+        # below) keeps the undropped dy.
+        dyd = ext.dropout_fwd(dy2, p, rng, site0 + 1) if rng is not None else dy2
         h1_2 = h1.view(-1, H)
         h2_2 = h2.view(-1, H)
         hip = _hip_gemms(dy2.shape[0], H)
@@ -215,8 +256,9 @@ class EncoderBlockFn(torch.autograd.Function):
                 dy2, w2.t().contiguous(), z1, act, scale8[3:4], amax8[3:4]
             )
         elif hip and z1.dtype == torch.float16:
-            # the forward saved g = act'(pre): dz1 = (dy @ W2) * g
-            dz1 = ext.gemm_nt_8p_gradmul(dy2, w2.t().contiguous(), z1)
+            # the forward saved g = act'(pre) (times the activation-site
+            # dropout mask, if any): dz1 = (dyd @ W2) * g
+            dz1 = ext.gemm_nt_8p_gradmul(dyd, w2.t().contiguous(), z1)
         elif hip:
             # dX of fc2 with the activation backward fused into the GEMM
             # epilogue: dz1 = (dy @ W2) * act'(z1) — no separate act_bwd pass
@@ -224,7 +266,7 @@ class EncoderBlockFn(torch.autograd.Function):
         else:
             df = torch.matmul(dy2, w2)
             dz1 = ext.act_bwd(df, z1, act)
-        dw2, db2 = _dw_db_gemm(ext, dy2, f, w2.dtype)
+        dw2, db2 = _dw_db_gemm(ext, dyd, f, w2.dtype)
         if fp8:
             w1t8, sw1 = _quant_e4m3_t(w1)
             dh2 = torch._scaled_mm(
@@ -271,10 +313,12 @@ class EncoderBlockFn(torch.autograd.Function):
             # next step's backward scale (delayed)
             scale8[3:4].copy_(torch.clamp(amax8[3:4] / 448.0, min=1e-12))
         return (dx, dln1w, dln1b, dwqkv, dbqkv, dwproj, dbproj, dln2w, dln2b,
-                dw1, db1, dw2, db2, None, None, None, None, None, None, None)
+                dw1, db1, dw2, db2, None, None, None, None, None, None, None,
+                None, None, None)
 
 
-def encoder_block(x, norm1, qkv, proj, norm2, fc1, fc2, *, num_heads, act, eps, causal, scale):
+def encoder_block(x, norm1, qkv, proj, norm2, fc1, fc2, *, num_heads, act, eps, causal, scale,
+                  p=0.0, rng=None, site0=0):
     from jimm_amd.ops.hip_linear import _FP8_STATE
 
     scale8 = amax8 = None
@@ -284,5 +328,5 @@ def encoder_block(x, norm1, qkv, proj, norm2, fc1, fc2, *, num_heads, act, eps, 
         x, norm1.weight, norm1.bias, qkv.weight, qkv.bias, proj.weight, proj.bias,
         norm2.weight, norm2.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
         scale8, amax8,
-        num_heads, act, eps, causal, scale,
+        num_heads, act, eps, causal, scale, p, rng, site0,
     )

@@ -34,6 +34,8 @@ class TrainConfig:
     warmup_steps: int = 0
     total_steps: int = 0
     min_lr: float = 0.0
+    # dropout masks are a function of (seed + dp_rank, step, site, element)
+    seed: int = 0
     extra: dict = field(default_factory=dict)
 
 
@@ -48,6 +50,11 @@ class Trainer:
         self.opt = Adam(model.parameters(), lr=cfg.lr, betas=cfg.betas, weight_decay=cfg.weight_decay)
         self.group = process_group
         self.step_idx = 0
+        # every data-parallel rank draws its own dropout masks
+        from jimm_amd import ops
+
+        rank = dist.get_rank(process_group) if dist.is_initialized() else 0
+        ops.set_dropout_seed(cfg.seed + rank)
         # JIMM_AMD_ROCTX=1: wrap each step in a roctx range (shows up in
         # rocprofv3 --marker-trace; SURVEY §5 tracing)
         import os
@@ -147,6 +154,9 @@ class Trainer:
         out["loss"] = loss.detach()
         return out
 
+    def _device(self) -> torch.device:
+        return next(self.model.parameters()).device
+
     def comm_stats(self) -> dict:
         """Per-step collective traffic (per-collective bytes).
 
@@ -166,8 +176,11 @@ class Trainer:
     # -- checkpoint / resume (the reference is load-only; we add
     # full trainer state so long runs are resumable) ------------------------
     def save_checkpoint(self, path: str) -> None:
-        """Rank-0 writes model + Adam state (moments, masters, step count)."""
+        """Rank-0 writes model + Adam state (moments, masters, step count)
+        and the dropout {seed, step}."""
         import torch.distributed as dist
+
+        from jimm_amd import ops
 
         if dist.is_initialized() and dist.get_rank(self.group) != 0:
             return
@@ -179,6 +192,7 @@ class Trainer:
                 "optimizer": self.opt.state_dict(),
                 "step_idx": self.step_idx,
                 "task": self.cfg.task,
+                "dropout_rng": list(ops.get_dropout_state(self._device())),
             },
             path,
         )
@@ -194,6 +208,15 @@ class Trainer:
                 if torch.is_tensor(v):
                     st[k] = v.to(dev)
         self.step_idx = ckpt["step_idx"]
+        if "dropout_rng" in ckpt:
+            # resume the mask sequence where the checkpoint left it (in place:
+            # a captured step keeps reading the same device tensor). Rank 0
+            # wrote its own seed; the others sit at seed + rank, as in __init__.
+            from jimm_amd import ops
+
+            seed, step = ckpt["dropout_rng"]
+            rank = dist.get_rank(self.group) if dist.is_initialized() else 0
+            ops.set_dropout_state(dev, seed + rank, step)
 
     @torch.no_grad()
     def eval_step(self, batch) -> dict[str, torch.Tensor]:
