@@ -250,12 +250,10 @@ void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> b
                 std::string act, c10::optional<torch::Tensor> residual, torch::Tensor y,
                 int save, c10::optional<torch::Tensor> z, const drop_args* drop);
 
+// Shapes and dtypes linear_fwd takes (whether it is used is the caller's
+// choice: JIMM_AMD_GEMM is read in Python, ops/hip_linear.py)
 bool gemm_supported(int64_t M, int64_t N, int64_t K, std::string dtype) {
-  if (dtype != "torch.bfloat16") return false;
-  if (K % BK != 0) return false;
-  const char* env = getenv("JIMM_AMD_GEMM");
-  if (env && std::string(env) == "blas") return false;
-  return true;
+  return dtype == "torch.bfloat16" && K % BK == 0;
 }
 
 namespace {

@@ -56,11 +56,10 @@
 // (no clamping — this is an accumulation).
 //
 // Split-M: grid.y walks m-chunks (slow index -> the chunk's operand rows
-// stay L3-resident across its output tiles).  Default combine: each split
-// writes a private fp32 slice of a workspace and ws_reduce_kernel folds
-// them in fixed order (deterministic), writing fp32 or bf16.  The fp32
-// atomicAdd combine into a zeroed C stays for A/B (JIMM_AMD_DW_WS=0);
-// grid.y == 1 stores once.
+// stay L3-resident across its output tiles).  Each split writes a private
+// fp32 slice of a workspace and ws_reduce_kernel folds them in fixed order
+// (deterministic), writing fp32 or bf16; grid.y == 1 stores once, straight
+// into C.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -112,7 +111,7 @@ __device__ __forceinline__ void img_inv(int o, int& m, int& col) {
   col = nt * 16 + u * 8;
 }
 
-template <bool ATOMIC, bool DBOUT = false, bool WSOUT = false>
+template <bool DBOUT, bool WSOUT>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
     const bf16* __restrict__ DZ, const bf16* __restrict__ X, float* __restrict__ C,
     int64_t M, int N, int Kw, int64_t chunk_m, float* __restrict__ DB) {
@@ -376,12 +375,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
         for (int ni = 0; ni < 4; ++ni) {
           const int k = k0 + wn * 64 + 16 * ni + lo;
           // WSOUT: each split owns a private C slice (no atomics; a reduce
-          // kernel folds the splits) — A/B alternative to the atomic
-          // combine, selected by JIMM_AMD_DW_WS=1
+          // kernel folds the splits)
           float* dst = C + (WSOUT ? (int64_t)blockIdx.y * N * Kw : 0) +
                        (int64_t)n * Kw + k;
-          if (ATOMIC && !WSOUT) atomicAdd(dst, acc[pr][mi][ni][r]);
-          else *dst = acc[pr][mi][ni][r];
+          *dst = acc[pr][mi][ni][r];
         }
       }
 }
@@ -477,52 +474,45 @@ static torch::Tensor tn8p_run(torch::Tensor dz, torch::Tensor x, float* dbp, int
   int splitm = (int)std::max<int64_t>(1, std::min<int64_t>(want, msteps));
   int64_t chunk = ((M + splitm - 1) / splitm + BMS - 1) / BMS * BMS;
   splitm = (int)((M + chunk - 1) / chunk);
-  // Workspace combine (default): each split writes a private C slice and a
-  // vectorized reduce folds them — measured 662-745 -> 684-824 TF/s over
-  // the fp32 atomic combine on the block shapes, and the fixed-order
-  // reduce makes the whole dW deterministic. JIMM_AMD_DW_WS=0 restores
-  // the atomic combine for A/B (nondeterministic accumulation order).
-  static const bool ws_mode = [] {
-    const char* e = getenv("JIMM_AMD_DW_WS");
-    return !(e && e[0] == '0');
-  }();
-  const bool use_ws = ws_mode && splitm > 1;
+  // More than one split: each writes a private C slice of a workspace and a
+  // vectorized reduce folds them in fixed order, so the whole dW is
+  // deterministic (measured 662-745 -> 684-824 TF/s over an fp32 atomic
+  // combine on the block shapes, profiles/r02_NOTES.md). One split stores
+  // straight into an fp32 C.
+  const bool use_ws = splitm > 1;
   const auto f32 = dz.options().dtype(torch::kFloat32);
   torch::Tensor C, ws;
   if (use_ws) {
     ws = torch::empty({(int64_t)splitm, (int64_t)N, (int64_t)Kw}, f32);
     C = torch::empty({(int64_t)N, (int64_t)Kw}, out_bf16 ? dz.options() : f32);
   } else {
-    C = splitm > 1 ? torch::zeros({(int64_t)N, (int64_t)Kw}, f32)
-                   : torch::empty({(int64_t)N, (int64_t)Kw}, f32);
+    C = torch::empty({(int64_t)N, (int64_t)Kw}, f32);
   }
   const size_t shmem = (size_t)RING * SLOT_BYTES;  // 160 KiB
-#define LAUNCH_TN(AT, DBO, WSO)                                                            \
-  launch_lds<gemm_tn_8p_kernel<AT, DBO, WSO>>(                                             \
+#define LAUNCH_TN(DBO, WSO)                                                                \
+  launch_lds<gemm_tn_8p_kernel<DBO, WSO>>(                                                 \
       dim3(tiles, splitm), dim3(NTHREADS), shmem, shmem, stream,                           \
       reinterpret_cast<const bf16*>(dz.data_ptr()),                                        \
       reinterpret_cast<const bf16*>(x.data_ptr()),                                         \
       WSO ? ws.data_ptr<float>() : C.data_ptr<float>(), M, N, Kw, chunk, dbp)
-  if (use_ws) {
-    if (dbp) LAUNCH_TN(false, true, true);
-    else LAUNCH_TN(false, false, true);
-    const int64_t n = (int64_t)N * Kw;
-    const int block = 256;
-    const int grid = (int)std::min<int64_t>((n / 4 + block - 1) / block, 8192);
-    if (out_bf16)
-      hipLaunchKernelGGL(ws_reduce_kernel<true>, dim3(grid), dim3(block), 0, stream,
-                         ws.data_ptr<float>(), C.data_ptr(), n, splitm);
-    else
-      hipLaunchKernelGGL(ws_reduce_kernel<false>, dim3(grid), dim3(block), 0, stream,
-                         ws.data_ptr<float>(), C.data_ptr(), n, splitm);
-    return C;
+  if (!use_ws) {
+    if (dbp) LAUNCH_TN(true, false);
+    else LAUNCH_TN(false, false);
+    return out_bf16 ? C.to(torch::kBFloat16) : C;
   }
-  if (dbp && splitm > 1) LAUNCH_TN(true, true, false);
-  else if (dbp) LAUNCH_TN(false, true, false);
-  else if (splitm > 1) LAUNCH_TN(true, false, false);
-  else LAUNCH_TN(false, false, false);
+  if (dbp) LAUNCH_TN(true, true);
+  else LAUNCH_TN(false, true);
 #undef LAUNCH_TN
-  return out_bf16 ? C.to(torch::kBFloat16) : C;
+  const int64_t n = (int64_t)N * Kw;
+  const int block = 256;
+  const int grid = (int)std::min<int64_t>((n / 4 + block - 1) / block, 8192);
+  if (out_bf16)
+    hipLaunchKernelGGL(ws_reduce_kernel<true>, dim3(grid), dim3(block), 0, stream,
+                       ws.data_ptr<float>(), C.data_ptr(), n, splitm);
+  else
+    hipLaunchKernelGGL(ws_reduce_kernel<false>, dim3(grid), dim3(block), 0, stream,
+                       ws.data_ptr<float>(), C.data_ptr(), n, splitm);
+  return C;
 }
 
 torch::Tensor gemm_tn_8p(torch::Tensor dz, torch::Tensor x, int64_t splitm, bool out_bf16) {

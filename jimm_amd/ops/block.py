@@ -26,14 +26,26 @@ import os
 import torch
 
 from jimm_amd.ops import _backend
-from jimm_amd.ops.hip_linear import _FP8_STATE, _dw_db_gemm, _dx_gemm, _gemm_mode
+from jimm_amd.ops.functional import _split_heads
+from jimm_amd.ops.hip_linear import (
+    _FP8_STATE,
+    _gemm_mode,
+    _quant_e4m3,
+    gemm_dw_db,
+    gemm_dx,
+    gemm_dx_act,
+    gemm_fwd,
+)
 from jimm_amd.ops.philox_dropout import dropout_threshold
 
 
-def _hip_gemms(M: int, H: int) -> bool:
-    """True when the encoder block's GEMMs run on the in-house MFMA kernels
-    (JIMM_AMD_GEMM=hip default; all block shapes have N%256==0, K%64==0)."""
-    return _gemm_mode() == "hip" and H % 256 == 0
+def _hip_gemms(H: int, mlp_dim: int) -> bool:
+    """True when the encoder block's forward GEMMs run on the in-house MFMA
+    kernels (JIMM_AMD_GEMM=hip, the default): H % 256 == 0 puts qkv, proj and
+    fc2 (N = 3H, H, H) on the 8-phase kernel, and every K (H or mlp_dim)
+    must be a multiple of 64 for any of them. fc1 (N = mlp_dim) takes the
+    128-tile kernels where mlp_dim % 256 != 0."""
+    return _gemm_mode() == "hip" and H % 256 == 0 and mlp_dim % 64 == 0
 
 
 def _act_save_g() -> bool:
@@ -65,21 +77,11 @@ def _fp8_block_state(mod: torch.nn.Module, device: torch.device):
     return st
 
 
-def _quant_e4m3_t(w: torch.Tensor):
-    """Quantize W^T to e4m3 (row-major (K, N) bytes): the column-major b
-    operand a scaled_mm dX GEMM (dz @ W) needs is its .t() view."""
-    s = (w.abs().amax().float() / 448.0).clamp(min=1e-12)
-    w8 = (w * s.reciprocal().to(w.dtype)).to(torch.float8_e4m3fn)  # (N, K) row-major
-    return w8.t().contiguous(), s  # (K, N); .t() at the call site is column-major
-
-
 def _mm_fp8q(y8: torch.Tensor, s: torch.Tensor, w: torch.Tensor,
              bias: torch.Tensor | None = None) -> torch.Tensor:
     """GEMM on a producer-emitted e4m3 activation (uint8 bytes + its scale)
     against a per-call-quantized e4m3 weight; bias fused in the hipBLASLt
     epilogue; bf16 out."""
-    from jimm_amd.ops.hip_linear import _quant_e4m3
-
     w8, sw = _quant_e4m3(w)
     return torch._scaled_mm(
         y8.view(torch.float8_e4m3fn), w8.t(), scale_a=s.view(1, 1),
@@ -125,7 +127,10 @@ class EncoderBlockFn(torch.autograd.Function):
         B, L, H = x.shape
         x = x.contiguous()
         x2 = x.view(-1, H)
-        hip = _hip_gemms(B * L, H)
+        # the engine of every bf16 GEMM below: the in-house MFMA kernels with
+        # the bias / act / residual epilogues fused into the GEMM kernel
+        # itself, or rocBLAS + the fused elementwise pass (gemm_fwd)
+        hip = _hip_gemms(H, w1.shape[0])
         # active dropout: site0 after the activation, site0 + 1 after fc2,
         # both under the {seed, step} snapshot rng (fused_block_enabled has
         # checked that the bf16 HIP save-g path below takes these shapes)
@@ -166,24 +171,13 @@ class EncoderBlockFn(torch.autograd.Function):
             qkv2 = _mm_fp8q(h1q, scale8[0:1], wqkv, bias=bqkv)
         else:
             h1, mean1, rstd1 = ext.layernorm_fwd(x, ln1w, ln1b, eps)
-            if hip:
-                # in-house MFMA GEMMs with the bias / act / residual epilogues
-                # fused into the GEMM kernel itself (csrc/gemm8p.hip)
-                qkv2, _ = ext.linear_fwd(h1.view(-1, H), wqkv, bqkv, "", None, False)
-            else:
-                qkv2 = torch.addmm(bqkv, h1.view(-1, H), wqkv.t())  # (M, 3H) fused bias
+            qkv2, _ = gemm_fwd(ext, h1.view(-1, H), wqkv, bqkv, None, None, hip=hip)  # (M, 3H)
         qkv = qkv2.view(B, L, 3, num_heads, H // num_heads)
-        q = qkv[:, :, 0].transpose(1, 2)
-        k = qkv[:, :, 1].transpose(1, 2)
-        v = qkv[:, :, 2].transpose(1, 2)
-        o, lse = ext.attn_fwd(q, k, v, causal, scale)            # (B,nh,L,d), (B,L,nh,d) storage
+        o, lse = ext.attn_fwd(*_split_heads(qkv), causal, scale)  # (B,nh,L,d), (B,L,nh,d) storage
         o2 = o.transpose(1, 2).reshape(-1, H)                    # free view
+        a, _ = gemm_fwd(ext, o2, wproj, bproj, None, x2, hip=hip)  # + bias + residual
+        a3 = a.view(B, L, H)
         if fp8:
-            if hip:
-                a, _ = ext.linear_fwd(o2, wproj, bproj, "", x2, False)
-            else:
-                a = ext.bias_act_fwd(torch.matmul(o2, wproj.t()), bproj, "", x2)
-            a3 = a.view(B, L, H)
             h2, h2q, mean2, rstd2 = ext.layernorm_fwd_fp8(
                 a3, ln2w, ln2b, eps, scale8[1:2], amax8[1:2]
             )
@@ -193,33 +187,21 @@ class EncoderBlockFn(torch.autograd.Function):
             # next step's forward scales (delayed); grad sites [3:5] are
             # updated at backward end, after their amax is collected
             scale8[0:3].copy_(torch.clamp(amax8[0:3] / 448.0, min=1e-12))
-        elif hip:
-            a, _ = ext.linear_fwd(o2, wproj, bproj, "", x2, False)
-            a3 = a.view(B, L, H)
+        else:
             h2, mean2, rstd2 = ext.layernorm_fwd(a3, ln2w, ln2b, eps)
             # fc2-dX runs as (M, mlp, H); where the 8-phase kernel takes it,
             # z1 holds the fp16 derivative act'(pre) instead of the
             # pre-activation (nothing else reads z1)
-            save_g = _act_save_g() and ext.gemm8p_supported(B * L, w1.shape[0], H)
+            save_g = hip and _act_save_g() and ext.gemm8p_supported(B * L, w1.shape[0], H)
             if drop and not save_g:
                 raise RuntimeError("fused block: dropout needs the saved-derivative fc1 path")
-            if save_g:
-                # with dropout f = act(z)*m*s and z1 = act'(z)*m*s: the mask
-                # of site0 reaches the backward inside the saved derivative
-                f, z1 = ext.linear_fwd_actgrad(h2.view(-1, H), w1, b1, act, None, p, rng, site0)
-            else:
-                f, z1 = ext.linear_fwd(h2.view(-1, H), w1, b1, act, None, True)
+            # with dropout f = act(z)*m*s and z1 = act'(z)*m*s: the mask of
+            # site0 reaches the backward inside the saved derivative
+            f, z1 = gemm_fwd(ext, h2.view(-1, H), w1, b1, act, None, hip=hip,
+                             save="g" if save_g else "z", drop=(p, rng, site0) if drop else None)
             # y = a + m*s*(f @ w2^T + b2) at site0 + 1
-            y, _ = ext.linear_fwd(f, w2, b2, "", a, False, p, rng, site0 + 1)
-        else:
-            a2 = torch.matmul(o2, wproj.t())
-            a = ext.bias_act_fwd(a2, bproj, "", x2)              # + bias + residual (one pass)
-            a3 = a.view(B, L, H)
-            h2, mean2, rstd2 = ext.layernorm_fwd(a3, ln2w, ln2b, eps)
-            z1 = torch.matmul(h2.view(-1, H), w1.t())
-            f = ext.bias_act_fwd(z1, b1, act, None)              # z1 -> pre-activation in place
-            y2 = torch.matmul(f, w2.t())
-            y = ext.bias_act_fwd(y2, b2, "", a)                  # + bias + residual
+            y, _ = gemm_fwd(ext, f, w2, b2, None, a, hip=hip,
+                            drop=(p, rng, site0 + 1) if drop else None)
         ctx.save_for_backward(x, ln1w, wqkv, wproj, ln2w, w1, w2,
                               h1, qkv, o, lse, a, mean1, rstd1, mean2, rstd2, h2, z1, f, rng)
         ctx.dims = (B, L, H, num_heads)
@@ -243,39 +225,33 @@ class EncoderBlockFn(torch.autograd.Function):
         dyd = ext.dropout_fwd(dy2, p, rng, site0 + 1) if rng is not None else dy2
         h1_2 = h1.view(-1, H)
         h2_2 = h2.view(-1, H)
-        hip = _hip_gemms(dy2.shape[0], H)
+        hip = _hip_gemms(H, w1.shape[0])
         fp8 = ctx.fp8_state is not None and hip
-        if fp8:
-            scale8, amax8 = ctx.fp8_state
 
         # MLP fc2 (+residual into a)
         if fp8:
+            scale8, amax8 = ctx.fp8_state
             # gradact dX with fused e4m3 emission of dz1; the fc1-dX GEMM
             # (dh2 = dz1 @ W1) then runs on the fp8 MFMA pipe
             dz1, dz18 = ext.gemm_nt_8p_gradact_fp8(
                 dy2, w2.t().contiguous(), z1, act, scale8[3:4], amax8[3:4]
             )
-        elif hip and z1.dtype == torch.float16:
-            # the forward saved g = act'(pre) (times the activation-site
-            # dropout mask, if any): dz1 = (dyd @ W2) * g
-            dz1 = ext.gemm_nt_8p_gradmul(dyd, w2.t().contiguous(), z1)
-        elif hip:
-            # dX of fc2 with the activation backward fused into the GEMM
-            # epilogue: dz1 = (dy @ W2) * act'(z1) — no separate act_bwd pass
-            dz1 = ext.gemm_nt_8p_gradact(dy2, w2.t().contiguous(), z1, act)
         else:
-            df = torch.matmul(dy2, w2)
-            dz1 = ext.act_bwd(df, z1, act)
-        dw2, db2 = _dw_db_gemm(ext, dyd, f, w2.dtype)
+            # z1 is the saved fp16 g = act'(pre) (times the activation-site
+            # dropout mask, if any): dz1 = (dyd @ W2) * g; or the bf16
+            # pre-activation: dz1 = (dy @ W2) * act'(z1), recomputed in the
+            # GEMM epilogue or in a separate act_bwd pass
+            dz1 = gemm_dx_act(ext, dyd, w2, z1, act, hip=hip)
+        dw2, db2 = gemm_dw_db(ext, dyd, f, w2.dtype)
         if fp8:
-            w1t8, sw1 = _quant_e4m3_t(w1)
+            w1t8, sw1 = _quant_e4m3(w1, transpose=True)
             dh2 = torch._scaled_mm(
                 dz18.view(torch.float8_e4m3fn), w1t8.t(), scale_a=scale8[3:4].view(1, 1),
                 scale_b=sw1.view(1, 1), out_dtype=torch.bfloat16,
             )
         else:
-            dh2 = _dx_gemm(ext, dz1, w1)
-        dw1, db1 = _dw_db_gemm(ext, dz1, h2_2, w1.dtype)
+            dh2 = gemm_dx(ext, dz1, w1)
+        dw1, db1 = gemm_dw_db(ext, dz1, h2_2, w1.dtype)
         # LN2 backward with the MLP residual grad (dy) fused into dx
         da3, dln2w, dln2b = ext.layernorm_bwd(
             dh2.view(B, L, H), a.view(B, L, H), ln2w, mean2, rstd2, dy.contiguous()
@@ -283,28 +259,21 @@ class EncoderBlockFn(torch.autograd.Function):
         da2 = da3.view(-1, H)
 
         # attention out-projection
-        do2 = _dx_gemm(ext, da2, wproj)
-        dwproj, dbproj = _dw_db_gemm(ext, da2, o.transpose(1, 2).reshape(-1, H), wproj.dtype)
+        do2 = gemm_dx(ext, da2, wproj)
+        dwproj, dbproj = gemm_dw_db(ext, da2, o.transpose(1, 2).reshape(-1, H), wproj.dtype)
         do_v = do2.view(B, L, nh, H // nh).permute(0, 2, 1, 3)   # (B,nh,L,d) strided view
 
         # fused flash attention backward straight into the strided dqkv
-        q = qkv[:, :, 0].transpose(1, 2)
-        k = qkv[:, :, 1].transpose(1, 2)
-        v = qkv[:, :, 2].transpose(1, 2)
         dqkv = torch.empty_like(qkv)
-        ext.attn_bwd_fused(
-            q, k, v, o, do_v, lse,
-            dqkv[:, :, 0].transpose(1, 2), dqkv[:, :, 1].transpose(1, 2),
-            dqkv[:, :, 2].transpose(1, 2), causal, scale,
-        )
+        ext.attn_bwd_fused(*_split_heads(qkv), o, do_v, lse, *_split_heads(dqkv), causal, scale)
         dqkv2 = dqkv.view(-1, 3 * H)
 
         # QKV projection. (qkv-dX stays bf16: quantizing dqkv needs a
         # standalone cast pass — measured a wash vs the fp8 GEMM saving,
         # and it costs dx accuracy. fc1-dX gets its e4m3 operand free from
         # the gradact epilogue, so only that dX runs fp8.)
-        dh1 = _dx_gemm(ext, dqkv2, wqkv)
-        dwqkv, dbqkv = _dw_db_gemm(ext, dqkv2, h1_2, wqkv.dtype)
+        dh1 = gemm_dx(ext, dqkv2, wqkv)
+        dwqkv, dbqkv = gemm_dw_db(ext, dqkv2, h1_2, wqkv.dtype)
         # LN1 backward with the attention residual grad (da) fused into dx
         dx, dln1w, dln1b = ext.layernorm_bwd(
             dh1.view(B, L, H), x, ln1w, mean1, rstd1, da3
@@ -319,8 +288,6 @@ class EncoderBlockFn(torch.autograd.Function):
 
 def encoder_block(x, norm1, qkv, proj, norm2, fc1, fc2, *, num_heads, act, eps, causal, scale,
                   p=0.0, rng=None, site0=0):
-    from jimm_amd.ops.hip_linear import _FP8_STATE
-
     scale8 = amax8 = None
     if _FP8_STATE["enabled"] and x.is_cuda and x.dtype == torch.bfloat16:
         scale8, amax8 = _fp8_block_state(norm1, x.device)

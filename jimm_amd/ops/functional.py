@@ -17,11 +17,12 @@ sites cited per op):
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 import torch.nn.functional as F
 
-from jimm_amd.ops import _backend
+from jimm_amd.ops import _backend, hip_linear
 
 # ---------------------------------------------------------------------------
 # activations
@@ -83,8 +84,9 @@ def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: f
 # ---------------------------------------------------------------------------
 
 
-def _strided_ok(t: torch.Tensor) -> bool:
-    return t.stride(3) == 1
+def _split_heads(qkv: torch.Tensor):
+    """qkv (B, L, 3, H, D), or its gradient -> the (B, H, L, D) views q, k, v."""
+    return qkv[:, :, 0].transpose(1, 2), qkv[:, :, 1].transpose(1, 2), qkv[:, :, 2].transpose(1, 2)
 
 
 def _attn_bwd_composite(ext, q, k, v, o, do, lse, causal, scale):
@@ -104,9 +106,18 @@ def _attn_bwd_composite(ext, q, k, v, o, do, lse, causal, scale):
 
 
 def _use_fused_bwd() -> bool:
-    import os
-
     return os.environ.get("JIMM_AMD_ATTN_BWD", "fused") == "fused"
+
+
+def _attn_bwd(ext, q, k, v, o, do, lse, dq, dk, dv, causal, scale) -> None:
+    """Attention backward into the caller's dq / dk / dv (strided views are
+    fine: the fused kernels read and write them with no permute copies; they
+    need a unit stride in the head dimension only)."""
+    if _use_fused_bwd() and all(t.stride(3) == 1 for t in (q, k, v, o, do, dq, dk, dv)):
+        ext.attn_bwd_fused(q, k, v, o, do, lse, dq, dk, dv, causal, scale)
+    else:
+        for dst, src in zip((dq, dk, dv), _attn_bwd_composite(ext, q, k, v, o, do, lse, causal, scale)):
+            dst.copy_(src)
 
 
 class _AttentionFn(torch.autograd.Function):
@@ -132,12 +143,8 @@ class _AttentionFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
-        ext = _backend.ext()
-        if _use_fused_bwd() and all(_strided_ok(t) for t in (q, k, v, o, do)):
-            dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-            ext.attn_bwd_fused(q, k, v, o, do, lse, dq, dk, dv, ctx.causal, ctx.scale)
-        else:
-            dq, dk, dv = _attn_bwd_composite(ext, q, k, v, o, do, lse, ctx.causal, ctx.scale)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        _attn_bwd(_backend.ext(), q, k, v, o, do, lse, dq, dk, dv, ctx.causal, ctx.scale)
         return dq, dk, dv, None, None
 
 
@@ -146,17 +153,14 @@ class _AttentionQKVFn(torch.autograd.Function):
 
     Input qkv: (B, L, 3, H, D) (a view of the (B,L,3H*D) GEMM output).
     Avoids autograd's per-slice backward (which materializes three
-    full-size zero tensors + scatter + add per layer): backward assembles
-    dqkv with three strided copies into one buffer.
+    full-size zero tensors + scatter + add per layer): backward writes dq /
+    dk / dv straight into the strided views of one dqkv buffer.
     Output: (B, H, L, D) view of (B,L,H,D) storage (free reshape to (B,L,HD)).
     """
 
     @staticmethod
     def forward(ctx, qkv, causal, scale):
-        q = qkv[:, :, 0].transpose(1, 2)
-        k = qkv[:, :, 1].transpose(1, 2)
-        v = qkv[:, :, 2].transpose(1, 2)
-        o, lse = _backend.ext().attn_fwd(q, k, v, causal, scale)
+        o, lse = _backend.ext().attn_fwd(*_split_heads(qkv), causal, scale)
         ctx.save_for_backward(qkv, o, lse)
         ctx.causal = causal
         ctx.scale = scale
@@ -165,25 +169,9 @@ class _AttentionQKVFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         qkv, o, lse = ctx.saved_tensors
-        scale = ctx.scale
-        ext = _backend.ext()
-        q = qkv[:, :, 0].transpose(1, 2)
-        k = qkv[:, :, 1].transpose(1, 2)
-        v = qkv[:, :, 2].transpose(1, 2)
         dqkv = torch.empty_like(qkv)
-        if _use_fused_bwd() and all(_strided_ok(t) for t in (o, do)):
-            # fused kernels write dq/dk/dv straight into the strided dqkv
-            # buffer — zero assembly copies
-            ext.attn_bwd_fused(
-                q, k, v, o, do, lse,
-                dqkv[:, :, 0].transpose(1, 2), dqkv[:, :, 1].transpose(1, 2),
-                dqkv[:, :, 2].transpose(1, 2), ctx.causal, scale,
-            )
-        else:
-            dq, dk, dv = _attn_bwd_composite(ext, q, k, v, o, do, lse, ctx.causal, scale)
-            dqkv[:, :, 0].transpose(1, 2).copy_(dq)
-            dqkv[:, :, 1].transpose(1, 2).copy_(dk)
-            dqkv[:, :, 2].transpose(1, 2).copy_(dv)
+        _attn_bwd(_backend.ext(), *_split_heads(qkv), o, do, lse, *_split_heads(dqkv),
+                  ctx.causal, ctx.scale)
         return dqkv, None, None
 
 
@@ -197,8 +185,7 @@ def attention_qkv(qkv: torch.Tensor, *, causal: bool = False, scale: float | Non
         scale = 1.0 / math.sqrt(qkv.shape[-1])
     if _backend.use_hip(qkv) and qkv.dtype == torch.bfloat16 and qkv.shape[-1] in (64, 72, 80, 96, 128):
         return _AttentionQKVFn.apply(qkv, causal, scale)
-    q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))
-    return attention(q, k, v, causal=causal, scale=scale)
+    return attention(*_split_heads(qkv), causal=causal, scale=scale)
 
 
 def attention(
@@ -241,22 +228,12 @@ def linear(
 ) -> torch.Tensor:
     """act(x @ weight.T + bias) [+ residual] with the epilogue fused on GPU."""
     if _backend.use_hip(x):
-        return _linear_hip(x, weight, bias, act, residual)
+        return hip_linear.linear_act(x, weight, bias, act, residual)
     y = F.linear(x, weight, bias)
     y = _act(y, act)
     if residual is not None:
         y = y + residual
     return y
-
-
-def _linear_hip(x, weight, bias, act, residual):
-    # Defined in terms of composable autograd pieces so backward is correct:
-    # the GEMM runs through torch.matmul (rocBLAS) or the in-house MFMA GEMM
-    # depending on JIMM_AMD_GEMM; bias+act(+residual) run in one fused HIP
-    # elementwise kernel with a fused backward.
-    import jimm_amd.ops.hip_linear as hip_linear
-
-    return hip_linear.linear_act(x, weight, bias, act, residual)
 
 
 # ---------------------------------------------------------------------------
@@ -272,8 +249,6 @@ def patch_embed(
     patch: int,
 ) -> torch.Tensor:
     if _backend.use_hip(img):
-        import jimm_amd.ops.hip_linear as hip_linear
-
         return hip_linear.patch_embed(img, weight, bias, patch)
     y = F.conv2d(img, weight, bias, stride=patch)  # (B, hidden, h, w)
     return y.flatten(2).transpose(1, 2)  # (B, n_patches, hidden)

@@ -1,18 +1,28 @@
-"""GPU linear / patch-embed path: GEMM + fused bias/activation/residual epilogue.
+"""GPU linear / patch-embed path, and the GEMM engine layer the fused encoder
+block (ops/block.py) shares with it.
 
-GEMM engine selection (env ``JIMM_AMD_GEMM``):
-  * ``hip`` (default) — in-house 8-phase 256-tile MFMA bf16 GEMM
-               (csrc/gemm8p.hip) with bias/act/residual/act-bwd epilogues
-               fused into the GEMM itself; dW on the split-M TN kernel
-               (csrc/gemm_tn8p.hip, fp32-exact); dX on the NT kernel over a
-               pre-transposed weight copy.
-  * ``blas`` — hipBLASLt/rocBLAS (with the committed MI355X TunableOp
-               table) + the separate fused bias+act(+residual) elementwise
-               kernel. Kept for A/B and for shapes the in-house kernels
-               do not cover (N % 256 != 0 or K % 64 != 0).
-  * fp8      — ``jimm_amd.ops.set_fp8(True)``: e4m3 scaled_mm forward and
-               plain-dX GEMMs (per-tensor dynamic device-side scales,
-               graph-capturable); gradact/dW/LN/losses stay bf16/fp32.
+Two engines run a GEMM:
+  * the in-house MFMA bf16 kernels: forward and dX on the NT kernels behind
+    ``ext.linear_fwd`` (the 8-phase 256-tile kernel of csrc/gemm8p.hip where
+    N % 256 == 0, K % 64 == 0 and K >= 128, else the 128-tile kernels of
+    csrc/gemm.hip for any K % 64 == 0), with the bias / activation / residual /
+    dropout epilogues and the activation backward fused into the GEMM; dW on
+    the split-M TN kernel (csrc/gemm_tn8p.hip, fp32 accumulate, N % 256 == 0
+    and K % 256 == 0), which can fold the bias gradient out of its operands;
+  * hipBLASLt/rocBLAS through torch (with the committed MI355X TunableOp
+    table) + the separate fused bias+act(+residual) elementwise kernel.
+
+How an engine runs a GEMM is written once, in ``gemm_fwd`` / ``gemm_dx`` /
+``gemm_dx_act`` / ``gemm_dw_db`` below. Which engine runs is each call site's
+own rule: ``JIMM_AMD_GEMM`` (``hip``, the default, or ``blas``; read by
+``_gemm_mode`` alone) and the shape predicates of the extension.
+``gemm_fwd`` and ``gemm_dx_act`` take the caller's choice as ``hip=``;
+``gemm_dx`` and ``gemm_dw_db`` gate per shape themselves.
+
+fp8 (``jimm_amd.ops.set_fp8(True)``): e4m3 scaled_mm forward GEMMs with
+per-tensor dynamic device-side scales (graph-capturable); the backward GEMMs,
+LN and losses stay bf16/fp32. The fused block has its own producer-fused
+fp8 arm (ops/block.py).
 """
 
 from __future__ import annotations
@@ -54,10 +64,13 @@ def _fp8_ok(x2: torch.Tensor, w: torch.Tensor) -> bool:
     )
 
 
-def _quant_e4m3(t: torch.Tensor):
+def _quant_e4m3(t: torch.Tensor, transpose: bool = False):
+    """Per-tensor e4m3 copy of t and its scale. transpose: the bytes of t^T,
+    row-major — the column-major b operand a scaled_mm dX GEMM (dz @ W) needs
+    is the .t() view of that."""
     scale = (t.abs().amax().float() / _FP8_MAX).clamp(min=1e-12)
     t8 = (t * scale.reciprocal().to(t.dtype)).to(torch.float8_e4m3fn)
-    return t8, scale
+    return (t8.t().contiguous() if transpose else t8), scale
 
 
 def _gemm_nt_fp8(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -69,10 +82,8 @@ def _gemm_nt_fp8(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 
 
 def _gemm_mode() -> str:
-    # Default "hip" (round 2): the 8-phase 256-tile MFMA GEMM (csrc/gemm8p)
-    # with epilogues (bias/act/residual/act-bwd) fused into the GEMM itself,
-    # plus the split-M TN dW kernel (csrc/gemm_tn8p). JIMM_AMD_GEMM=blas
-    # switches back to hipBLASLt/rocBLAS + separate elementwise passes.
+    # "hip" (default): the in-house MFMA GEMMs with fused epilogues;
+    # JIMM_AMD_GEMM=blas: hipBLASLt/rocBLAS + separate elementwise passes.
     return os.environ.get("JIMM_AMD_GEMM", "hip")
 
 
@@ -80,48 +91,38 @@ def _deterministic() -> bool:
     return os.environ.get("JIMM_AMD_DETERMINISTIC", "0") == "1"
 
 
-def _dw_ws() -> bool:
-    # default workspace+fixed-order-reduce combine (deterministic);
-    # JIMM_AMD_DW_WS=0 selects the atomic combine (A/B only)
-    return os.environ.get("JIMM_AMD_DW_WS", "1") != "0"
+# ---------------------------------------------------------------------------
+# GEMM engine layer
+# ---------------------------------------------------------------------------
 
 
-def _dw_gemm(ext, dz: torch.Tensor, x2: torch.Tensor, out_dtype) -> torch.Tensor:
-    """dW = dz^T @ x2 — in-house split-M TN kernel (fp32 accumulate; the
-    default workspace combine is deterministic, so deterministic mode only
-    falls back when JIMM_AMD_DW_WS=0 forces the atomic combine)."""
-    if (
-        _gemm_mode() == "hip"
-        and (_dw_ws() or not _deterministic())
-        and dz.dtype == torch.bfloat16
-        and ext.gemm_tn8p_supported(dz.shape[0], dz.shape[1], x2.shape[1])
-    ):
-        # bf16 weights: the split reduce rounds to bf16 itself (no cast pass)
-        return ext.gemm_tn_8p(dz, x2, 0, out_dtype == torch.bfloat16).to(out_dtype)
-    return torch.matmul(dz.t(), x2)
+def gemm_fwd(ext, x2, w, b, act, res2, *, hip: bool, save=None, drop=None):
+    """y = act(x2 @ w^T + b) [+ res2] -> (y, saved). save: None, "z" (the
+    bf16 pre-activation) or "g" (the fp16 derivative act'(pre), in-house
+    engine only). drop = (p, rng, site): dropout fused into the in-house
+    epilogue. hip is the caller's engine choice."""
+    act = act or ""
+    if hip:
+        drop = drop or ()
+        if save == "g":
+            y, saved = ext.linear_fwd_actgrad(x2, w, b, act, res2, *drop)
+        else:
+            y, saved = ext.linear_fwd(x2, w, b, act, res2, save == "z", *drop)
+        return y, saved
+    if save == "g" or drop is not None:
+        raise RuntimeError("gemm_fwd: the saved derivative and fused dropout need the HIP GEMMs")
+    if not act and res2 is None and b is not None:
+        # bias-only: hipBLASLt fuses the bias epilogue into the GEMM —
+        # no separate full-tensor bias pass
+        return torch.addmm(b, x2, w.t()), None
+    z = torch.matmul(x2, w.t())
+    # fused bias+act(+residual): z is updated in place to hold the
+    # pre-activation (z+bias); y aliases z when there is no act.
+    y = ext.bias_act_fwd(z, b, act, res2)
+    return y, (z if save else None)
 
 
-def _dw_db_gemm(ext, dz: torch.Tensor, x2: torch.Tensor, out_dtype):
-    """dW AND the bias grad in one kernel: db = colsum(dz) is folded out of
-    the dW kernel's dz fragments (already in registers) instead of a
-    separate full re-read of dz (csrc/gemm_tn8p.hip DBOUT)."""
-    if (
-        _gemm_mode() == "hip"
-        and not _deterministic()
-        and dz.dtype == torch.bfloat16
-        and ext.gemm_tn8p_supported(dz.shape[0], dz.shape[1], x2.shape[1])
-    ):
-        dw, db = ext.gemm_tn_8p_db(dz, x2, 0, out_dtype == torch.bfloat16)
-        return dw.to(out_dtype), db.to(dz.dtype)
-    dw = torch.matmul(dz.t(), x2)
-    if dz.is_cuda and dz.shape[-1] % 8 == 0:
-        db = _backend.ext().colsum(dz).to(dz.dtype)
-    else:
-        db = dz.sum(dim=0)
-    return dw, db
-
-
-def _dx_gemm(ext, dz: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+def gemm_dx(ext, dz: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """dX = dz @ w — in-house NT kernel on a pre-transposed weight copy.
 
     (Per-call-quantized fp8 dX was measured NET-NEGATIVE at config 5: the
@@ -139,9 +140,50 @@ def _dx_gemm(ext, dz: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return torch.matmul(dz, w)
 
 
-def _gemm_nt(x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """z = x2 @ w.T  — (N,K)@(M,K)^T -> (N,M), no epilogue."""
-    return torch.matmul(x2, w.t())
+def gemm_dx_act(ext, dy2, w, saved, act, *, hip: bool) -> torch.Tensor:
+    """dz = (dy2 @ w) * act'(pre), the dX of an activated linear, from what
+    its forward saved: the fp16 derivative (one multiply in the epilogue), or
+    the bf16 pre-activation — the derivative recomputed in the epilogue where
+    the caller's engine is the in-house one (hip) and the 8-phase kernel
+    takes the shape, else rocBLAS + a separate act_bwd pass."""
+    if saved.dtype == torch.float16:
+        return ext.gemm_nt_8p_gradmul(dy2, w.t().contiguous(), saved)
+    if hip and ext.gemm8p_supported(dy2.shape[0], w.shape[1], w.shape[0]):
+        return ext.gemm_nt_8p_gradact(dy2, w.t().contiguous(), saved, act)
+    return ext.act_bwd(torch.matmul(dy2, w), saved, act)
+
+
+def _colsum(ext, dz: torch.Tensor) -> torch.Tensor:
+    """The bias gradient on its own: one fp32-accumulating pass over dz."""
+    if dz.is_cuda and dz.shape[-1] % 8 == 0:
+        return ext.colsum(dz).to(dz.dtype)
+    return dz.sum(dim=0)
+
+
+def gemm_dw_db(ext, dz, x2, out_dtype, need_dw: bool = True, need_db: bool = True):
+    """(dW = dz^T @ x2 | None, db = colsum(dz) | None). The in-house split-M
+    TN kernel (fp32 accumulate, deterministic fixed-order combine of the
+    splits; bf16 weights: the combine rounds to bf16 itself, no cast pass)
+    folds db out of the dz fragments it already holds in registers instead
+    of a separate full re-read of dz. That fold adds fp32 atomically, so
+    deterministic mode does not take it."""
+    tn = (
+        need_dw
+        and _gemm_mode() == "hip"
+        and dz.dtype == torch.bfloat16
+        and ext.gemm_tn8p_supported(dz.shape[0], dz.shape[1], x2.shape[1])
+    )
+    if tn and need_db and not _deterministic():
+        dw, db = ext.gemm_tn_8p_db(dz, x2, 0, out_dtype == torch.bfloat16)
+        return dw.to(out_dtype), db.to(dz.dtype)
+    dw = db = None
+    if tn and not need_db:
+        dw = ext.gemm_tn_8p(dz, x2, 0, out_dtype == torch.bfloat16).to(out_dtype)
+    elif need_dw:
+        dw = torch.matmul(dz.t(), x2)
+    if need_db:
+        db = _colsum(ext, dz)
+    return dw, db
 
 
 class _LinearActFn(torch.autograd.Function):
@@ -154,17 +196,9 @@ class _LinearActFn(torch.autograd.Function):
         if _FP8_STATE["enabled"] and _fp8_ok(x2, w):
             z = _gemm_nt_fp8(x2, w)
             y = ext.bias_act_fwd(z, b, act or "", res2)
-        elif _gemm_mode() == "hip" and ext.gemm_supported(x2.shape[0], out_f, in_f, str(x2.dtype)):
-            y, z = ext.linear_fwd(x2, w, b, act or "", res2, act is not None)
-        elif act is None and res2 is None and b is not None:
-            # bias-only: hipBLASLt fuses the bias epilogue into the GEMM —
-            # no separate full-tensor bias pass
-            y = z = torch.addmm(b, x2, w.t())
         else:
-            z = _gemm_nt(x2, w)
-            # fused bias+act(+residual): z is updated in place to hold the
-            # pre-activation (z+bias); y aliases z when there is no act.
-            y = ext.bias_act_fwd(z, b, act or "", res2)
+            hip = _gemm_mode() == "hip" and ext.gemm_supported(x2.shape[0], out_f, in_f, str(x2.dtype))
+            y, z = gemm_fwd(ext, x2, w, b, act, res2, hip=hip, save="z" if act is not None else None)
         if act is not None:
             ctx.save_for_backward(x2, w, z)
         else:
@@ -182,25 +216,12 @@ class _LinearActFn(torch.autograd.Function):
             x2, w, z = ctx.saved_tensors
         else:
             x2, w = ctx.saved_tensors
-            z = None
-        dy2 = dy.contiguous().reshape(-1, dy.shape[-1])
-        if ctx.act is not None:
-            dz = _backend.ext().act_bwd(dy2, z, ctx.act)
-        else:
-            dz = dy2
         ext = _backend.ext()
-        dx = _dx_gemm(ext, dz, w).view(ctx.x_shape) if ctx.needs_input_grad[0] else None
-        if ctx.needs_input_grad[1] and ctx.has_bias and ctx.needs_input_grad[2]:
-            dw, db = _dw_db_gemm(ext, dz, x2, w.dtype)
-        else:
-            dw = _dw_gemm(ext, dz, x2, w.dtype) if ctx.needs_input_grad[1] else None
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                if dz.is_cuda and dz.shape[-1] % 8 == 0:
-                    db = _backend.ext().colsum(dz).to(dz.dtype)
-                else:
-                    db = dz.sum(dim=0)
-            else:
-                db = None
+        dy2 = dy.contiguous().reshape(-1, dy.shape[-1])
+        dz = ext.act_bwd(dy2, z, ctx.act) if ctx.act is not None else dy2
+        dx = gemm_dx(ext, dz, w).view(ctx.x_shape) if ctx.needs_input_grad[0] else None
+        dw, db = gemm_dw_db(ext, dz, x2, w.dtype, ctx.needs_input_grad[1],
+                            ctx.has_bias and ctx.needs_input_grad[2])
         dres = dy.view(ctx.res_shape) if (ctx.has_res and ctx.needs_input_grad[4]) else None
         return dx, dw, db, None, dres
 
@@ -225,15 +246,17 @@ class _PatchEmbedFn(torch.autograd.Function):
         ext = _backend.ext()
         cols = ext.im2col_patch(img.contiguous(), patch)  # (B*h*w, C*P*P)
         w2 = w.reshape(w.shape[0], -1).contiguous()  # (hidden, C*P*P)
-        if (
+        hip = (
             _gemm_mode() == "hip"
             and cols.dtype == torch.bfloat16
             and ext.gemm8p_supported(cols.shape[0], w2.shape[0], w2.shape[1])
-        ):
-            y, _ = ext.linear_fwd(cols, w2, b, "", None, False)
+        )
+        if hip:
+            y, _ = gemm_fwd(ext, cols, w2, b, None, None, hip=True)
         else:
-            z = _gemm_nt(cols, w2)
-            y = ext.bias_act_fwd(z, b, "", None)
+            # not gemm_fwd's rocBLAS arm, whose bias-only case is addmm: this
+            # path adds the bias in a separate pass, and its numbers stay
+            y = ext.bias_act_fwd(torch.matmul(cols, w2.t()), b, "", None)
         ctx.save_for_backward(cols, w2)
         ctx.img_shape = img.shape
         ctx.patch = patch
@@ -247,17 +270,13 @@ class _PatchEmbedFn(torch.autograd.Function):
         patch = ctx.patch
         ext = _backend.ext()
         dy2 = dy.contiguous().reshape(-1, dy.shape[-1])
-        dcols = _dx_gemm(ext, dy2, w2)
+        dcols = gemm_dx(ext, dy2, w2)
         dimg = ext.col2im_patch(dcols, list(ctx.img_shape), patch) if ctx.needs_input_grad[0] else None
-        dw = _dw_gemm(ext, dy2, cols, w2.dtype).view(ctx.w_shape) if ctx.needs_input_grad[1] else None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            if dy2.shape[-1] % 8 == 0:
-                db = _backend.ext().colsum(dy2).to(dy2.dtype)
-            else:
-                db = dy2.sum(dim=0)
-        else:
-            db = None
-        return dimg, dw, db, None
+        # dW alone, db by the separate colsum: this path does not use the
+        # TN kernel's db fold
+        dw, _ = gemm_dw_db(ext, dy2, cols, w2.dtype, ctx.needs_input_grad[1], need_db=False)
+        db = _colsum(ext, dy2) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dimg, dw.view(ctx.w_shape) if dw is not None else None, db, None
 
 
 def patch_embed(img, w, b, patch):

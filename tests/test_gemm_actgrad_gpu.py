@@ -171,7 +171,7 @@ def test_block_save_g_vs_save_z(act, monkeypatch):
     blk = EncoderBlock(256, 4, 512, hidden_act=act, layernorm_epsilon=1e-6).to(dev(), torch.bfloat16)
     x = torch.randn(2, 40, 256, device=dev()).bfloat16()
     dy = torch.randn_like(x)
-    assert block_mod.fused_block_enabled(x, 0.0) and block_mod._hip_gemms(80, 256)
+    assert block_mod.fused_block_enabled(x, 0.0) and block_mod._hip_gemms(256, 512)
 
     calls = []
     for name in ("gemm_nt_8p_gradmul", "gemm_nt_8p_gradact"):
