@@ -31,7 +31,7 @@ FLOOR_STEP_VIT_B1024 = 5500  # img/s (r02 final: 5753)
 FLOORS_GEMM = {  # (M, N, K, act): fwd_tf
     (201728, 2304, 768, ""): 790,
     (201728, 3072, 768, "gelu"): 624,  # hardware-rcp erf + hoisted bias: 0.9 x measured 695 / 696 / 694
-    (201728, 768, 3072, ""): 890,
+    (201728, 768, 3072, ""): 973,  # 4-wide epilogue (8-byte accesses): 0.9 x measured 1079 / 1101 / 1082
 }
 FLOORS_DW = {  # (M, N, K): tf (staging ring + round-aware splits; 0.9 x measured 953 / 980 / 970)
     (201728, 2304, 768): 855,

@@ -40,6 +40,26 @@
 // row-XOR spreads them over all 16 slots).  glds writes lane-linear; the
 // inverse permutation goes on the per-lane SOURCE address (§5.4 rule 21).
 //
+// Column mapping. In the MFMA accumulator layout a lane owns fragment column
+// lo of each of its 4 B-fragments, i.e. columns 16*ni + lo of its wave's 64
+// when image row j of a B half-image holds W row j: four columns 16 apart,
+// every epilogue access 2 bytes wide. The non-dropout kernels (PERM = !DROP)
+// instead stage W row 4*(j & 15) + ((j >> 4) & 3) of each 64-row group into
+// image row j. Only the per-lane glds SOURCE row changes (stage_base): the
+// image, its swizzle, offB / frag_off, every ds_read, wait and barrier of the
+// K loop are what they were, and acc[pr][mi][ni][r] is now column 4*lo + ni —
+// the same sum of the same products in the same order, so the same
+// accumulator bits (what the epilogue makes of them: gemm_epilogue4, mfma.h).
+// A lane's 4 values of a row are 4 consecutive columns, and gemm_epilogue4
+// (mfma.h) makes one access per stream for them: 8 bytes of Y, Z / g,
+// residual or saved z / g, 4 bytes of e4m3, and the 4 bias values in one
+// 16-byte (fp32) or 8-byte (bf16) load per tile. 16 lanes cover 128
+// contiguous bytes of a row.
+// The DROP kernels keep the unpermuted mapping and the per-element epilogue:
+// the dropout definition (docs/kernels.md) gives one Philox call to columns
+// {c, c+16, c+32, c+48}, exactly the 4 columns a lane owns there; with 4
+// consecutive columns a lane would make four calls and use one word of each.
+//
 // Epilogue fuses bias (fp32 or bf16, a lane's 4 values loaded once) +
 // gelu/gelu_tanh/quickgelu (+residual) and saves nothing, the bf16
 // pre-activation or the fp16 activation derivative (SAVE_*, mfma.h); the dX
@@ -49,7 +69,10 @@
 // into the two forward forms the MLP has: a lane's 16 elements of a fragment
 // are the 4 words x 2 halves of two Philox calls, made in the epilogue loops.
 // M may be ragged (MGUARD clamps staging rows and predicates stores);
-// N%256==0, K%64==0, K>=128 required (gemm8p_supported).
+// N%256==0, K%64==0, K>=128 required (gemm8p_supported). The 8-byte accesses
+// need 8-byte aligned y / residual / z / g and bf16 bias, a 16-byte aligned
+// fp32 bias and a 4-byte aligned e4m3 output; N%256==0 keeps every row and
+// column offset aligned, the base pointers are checked in launch_8p.
 
 #include <torch/extension.h>
 #include <hip/hip_fp8.h>
@@ -70,14 +93,20 @@ constexpr int HALF_BYTES = 128 * BK * 2;  // 16 KiB per half-image
 // only the K offset advances — the K-loop adds kt*128 B).  A half-image is
 // staged by 512 threads x 16 B x 2 rounds; round r, thread tid covers image
 // byte off = r*8192 + tid*16.
-template <bool MGUARD>
+//
+// PERM (the W operand of the non-dropout kernels): image row j takes source
+// row (j & ~63) + 4*(j & 15) + ((j >> 4) & 3) instead of row j.
+// The image, its swizzle and every read of it are the same; a fragment row
+// 16*ni + lo now holds column 4*lo + ni. A lane still reads 16 contiguous
+// bytes and 8 lanes one 128-byte row segment.
+template <bool MGUARD, bool PERM = false>
 __device__ __forceinline__ const bf16* stage_base(const bf16* __restrict__ gsrc,
                                                   int64_t ldg, int row0, int rows_total,
                                                   int round, int tid) {
   const int off = round * 8192 + tid * 16;
   const int row = off >> 7;
   const int chunk = ((off >> 4) & 7) ^ (row & 7);
-  int grow = row0 + row;
+  int grow = row0 + (PERM ? (row & ~63) + 4 * (row & 15) + ((row >> 4) & 3) : row);
   if (MGUARD) grow = grow < rows_total ? grow : rows_total - 1;
   return gsrc + (int64_t)grow * ldg + chunk * 8;
 }
@@ -106,6 +135,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
     return smem + 4 * HALF_BYTES + (slot * 2 + h) * HALF_BYTES;
   };
 
+  // column mapping of a lane's accumulators (file header)
+  constexpr bool PERM = !DROP;
+
   const int tid = threadIdx.x;
   const int lane = tid % WAVE;
   const int wave = tid / WAVE;
@@ -130,7 +162,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       asrc[h][r] = stage_base<MGUARD>(X, K, m0 + h * 128, M, r, tid);
-      bsrc[h][r] = stage_base<false>(W + (int64_t)n0 * K, K, h * 128, N, r, tid);
+      bsrc[h][r] = stage_base<false, PERM>(W + (int64_t)n0 * K, K, h * 128, N, r, tid);
     }
   const int ldst = tid * 16;  // lds dest byte of round 0
   auto stageA = [&](int kt, int h) {
@@ -224,15 +256,19 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
   }
 
   // Epilogue: acc[pr][mi][ni] -> rows m0 + pr*128 + wm*64 + 16mi + hi*4 + r,
-  // cols n0 + wn*64 + 16ni + lo.
+  // cols n0 + wn*64 + 4lo + ni (PERM) or n0 + wn*64 + 16ni + lo (DROP).
   float rs8 = 1.f, tmax = 0.f;
   if (FP8O) rs8 = fast_rcpf(scale8[0]);
   // a lane owns 4 columns (n depends on ni alone): its bias values, once
   float bv[4] = {};
   if (HAS_BIAS) {
+    if constexpr (PERM) {
+      load_bias4(bias, n0 + wn * 64 + 4 * lo, bias_bf16, bv);
+    } else {
 #pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-      bv[ni] = load_bias(bias, n0 + wn * 64 + 16 * ni + lo, bias_bf16);
+      for (int ni = 0; ni < 4; ++ni)
+        bv[ni] = load_bias(bias, n0 + wn * 64 + 16 * ni + lo, bias_bf16);
+    }
   }
   if constexpr (DROP) {
     // A lane's 16 elements of a fragment are rows hi*4 + {0..3} x columns
@@ -266,6 +302,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
       }
     }
   } else {
+    // a row's 4 values of a lane are 4 consecutive columns: one call, one
+    // 8-byte access per stream
+    const int n = n0 + wn * 64 + 4 * lo;
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
 #pragma unroll
@@ -274,12 +313,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
         for (int r = 0; r < 4; ++r) {
           const int m = m0 + pr * 128 + wm * 64 + 16 * mi + hi * 4 + r;
           if (MGUARD && m >= M) continue;
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni) {
-            const int n = n0 + wn * 64 + 16 * ni + lo;
-            gemm_epilogue<ACT, HAS_BIAS, HAS_RES, SAVE, GRADM, FP8O>(
-                acc[pr][mi][ni][r], m, n, N, bv[ni], res, Y, Z, Y8, rs8, &tmax);
-          }
+          const float v4[4] = {acc[pr][mi][0][r], acc[pr][mi][1][r], acc[pr][mi][2][r],
+                               acc[pr][mi][3][r]};
+          gemm_epilogue4<ACT, HAS_BIAS, HAS_RES, SAVE, GRADM, FP8O>(v4, m, n, N, bv, res, Y, Z,
+                                                                    Y8, rs8, &tmax);
         }
       }
     }
@@ -300,12 +337,23 @@ namespace {
 
 // One launch of a gemm_nt_8p_kernel instantiation: 160 KiB of LDS (the full
 // CU), one workgroup per 256x256 output tile.
-template <auto Kernel>
+template <auto Kernel, bool WIDE = true>
 void launch_8p(const torch::Tensor& x, const torch::Tensor& w, const void* biasp, int bias_bf16,
                const bf16* resp, torch::Tensor& y, bf16* zp, unsigned char* y8p = nullptr,
                const float* scale8p = nullptr, unsigned int* amaxp = nullptr,
                drop_args drop = {}) {
   const int M = x.size(0), K = x.size(1), N = w.size(0);
+  // the 4-wide epilogue's vector accesses (N % 256 == 0 keeps every row and
+  // column offset a multiple of the access; the bases are the callers'). WIDE
+  // is false for the dropout kernels, whose accesses stay 2 bytes wide.
+  if (WIDE) {
+    auto aligned = [](const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; };
+    TORCH_CHECK(aligned(y.data_ptr(), 8) && aligned(resp, 8) && aligned(zp, 8) && aligned(y8p, 4),
+                "8-phase GEMM: y, residual / z / g and the saved tensor must be 8-byte aligned, "
+                "the e4m3 output 4-byte aligned");
+    TORCH_CHECK(aligned(biasp, bias_bf16 ? 8 : 16),
+                "8-phase GEMM: a bf16 bias must be 8-byte, an fp32 bias 16-byte aligned");
+  }
   constexpr size_t shmem = 10 * HALF_BYTES;
   const int mt = (M + BM - 1) / BM;
   launch_lds<Kernel>(dim3(mt * (N / BN)), dim3(NTHREADS), shmem, shmem,
@@ -418,8 +466,9 @@ void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> b
             } else if (drop) {
               if constexpr (fc1 || fc2) {
                 launch_8p<gemm_nt_8p_kernel<A, true, HR, S, decltype(mg)::value, GRADM_NONE,
-                                            false, true>>(x, w, biasp, bias_bf16, resp, y, zp,
-                                                          nullptr, nullptr, nullptr, *drop);
+                                            false, true>,
+                          false>(x, w, biasp, bias_bf16, resp, y, zp, nullptr, nullptr, nullptr,
+                                 *drop);
               } else {
                 TORCH_CHECK(false, "dropout epilogue: only act + bias + saved derivative (fc1) "
                                    "or bias + residual (fc2)");

@@ -236,6 +236,108 @@ __device__ __forceinline__ void gemm_epilogue(float vpre, int m, int n, int N, f
   }
 }
 
+// bias[n .. n+3] as fp32, n a multiple of 4: one 16-byte fp32 or one 8-byte
+// bf16 load (the vector must be 16- resp. 8-byte aligned).
+__device__ __forceinline__ void load_bias4(const void* bias, int n, int bias_bf16,
+                                           float (&b)[4]) {
+  if (bias_bf16) vload_f32<4>(static_cast<const bf16*>(bias) + n, b);
+  else vload_f32<4>(static_cast<const float*>(bias) + n, b);
+}
+
+// Makes x depend on tok without changing it (no instruction): what is
+// computed from x can then neither be hoisted above tok nor be paired with the
+// computation of tok.
+// The same with nothing to wait for: what consumes x (a packed store) is cut
+// off from what computed it.
+__device__ __forceinline__ void opaque(float& x) { asm("" : "+v"(x)); }
+__device__ __forceinline__ void opaque(unsigned int& x) { asm("" : "+v"(x)); }
+__device__ __forceinline__ void after(float& x, float tok) { asm("" : "+v"(x) : "v"(tok)); }
+__device__ __forceinline__ void after(float& x, unsigned int tok) {
+  asm("" : "+v"(x) : "v"(tok));
+}
+
+// gemm_epilogue for the 4 consecutive columns n .. n+3 (n a multiple of 4) of
+// row m that a lane of the column-permuted 8-phase kernel holds (gemm8p.hip):
+// every stream is one access (8 bytes of bf16 or fp16, 4 bytes of e4m3)
+// instead of four. Y, Z and res must be 8-byte aligned, Y8 4-byte, and N a
+// multiple of 4. No dropout form: its Philox words are tied to the 16-apart
+// columns of the unpermuted kernel.
+// Per element it is gemm_epilogue's arithmetic, and it has to compile to
+// gemm_epilogue's instructions as well. Four independent copies of the
+// activation code in a row get packed in pairs (v_pk_mul_f32, v_pk_add_f32)
+// BEFORE multiplies and adds are contracted, which leaves fewer fmas than the
+// per-element code has (tanh-GELU: x2 * c + 1 and 1 - t * t stay unfused) and
+// replaces the fp16 derivative's single rounding (v_fma_mixlo_f16) by a
+// packed fma and a conversion: other rounding points, other bits. So with an
+// activation the elements are chained and closed off: element j's inputs come
+// `after` element j - 1's results, and its results are `opaque` to the packed
+// stores, so the vectoriser finds no group of like operations to start from,
+// across the elements. erf-GELU and QuickGELU then compile to gemm_epilogue's
+// instructions per element (same bits). tanh-GELU does not quite: the
+// compiler also pairs two like operations INSIDE one element (1 - 2r with
+// 1 + c*x^2) and leaves them unfused, here in every kernel, under
+// gemm_epilogue in some; those results agree to rounding, not bit for bit.
+// Without an activation there is nothing to contract (adds, or one multiply)
+// and the packing is left alone.
+template <int ACT, bool HAS_BIAS, bool HAS_RES, int SAVE, int GRADM = GRADM_NONE,
+          bool FP8O = false>
+__device__ __forceinline__ void gemm_epilogue4(const float (&acc4)[4], int m, int n, int N,
+                                               const float (&bias4)[4], const bf16* res, bf16* Y,
+                                               bf16* Z, unsigned char* Y8 = nullptr,
+                                               float rs8 = 1.f, float* tmax = nullptr) {
+  static_assert(SAVE != SAVE_GRAD || ACT != ACT_NONE, "SAVE_GRAD needs an activation");
+  typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+  constexpr bool READS = GRADM != GRADM_NONE || HAS_RES;  // res holds a residual, z or g
+  constexpr bool CHAIN = ACT != ACT_NONE;
+  const int64_t at = (int64_t)m * N + n;
+  float vpre[4], vy[4], in4[4] = {};
+  u16x4 g4 = {};
+  if (GRADM == GRADM_MUL) {
+    const u16x4 h4 = *reinterpret_cast<const u16x4*>(res + at);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) in4[j] = __half2float(__ushort_as_half(h4[j]));
+  } else if (READS) {
+    vload_f32<4>(res + at, in4);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    vpre[j] = HAS_BIAS ? acc4[j] + bias4[j] : acc4[j];
+    if (CHAIN && j > 0) {
+      after(vpre[j], vy[j - 1]);
+      if (READS) after(in4[j], vy[j - 1]);
+      if (SAVE == SAVE_GRAD) after(vpre[j], (unsigned int)g4[j - 1]);
+    }
+    if (GRADM == GRADM_ACT) {
+      vy[j] = vpre[j] * act_grad(in4[j], ACT);
+    } else if (GRADM == GRADM_MUL) {
+      vy[j] = vpre[j] * in4[j];
+    } else {
+      if (SAVE == SAVE_GRAD) {
+        float g;
+        vy[j] = act_fwd_grad(vpre[j], ACT, &g);
+        unsigned int gb = __half_as_ushort(__float2half(g));
+        if (CHAIN) opaque(gb);
+        g4[j] = (unsigned short)gb;
+      } else {
+        vy[j] = act_fwd(vpre[j], ACT);
+      }
+      if (HAS_RES) vy[j] += in4[j];
+    }
+    if (CHAIN) opaque(vy[j]);
+  }
+  if (SAVE == SAVE_PRE) vstore_f32<4>(Z + at, vpre);
+  if (SAVE == SAVE_GRAD) *reinterpret_cast<u16x4*>(Z + at) = g4;
+  vstore_f32<4>(Y + at, vy);
+  if (FP8O) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) *tmax = fmaxf(*tmax, fabsf(vy[j]));
+    // cvt_e4m3(a) is the low byte of cvt2_e4m3(a, .), b's byte is the next one
+    *reinterpret_cast<unsigned int*>(Y8 + at) =
+        (unsigned int)cvt2_e4m3(vy[0] * rs8, vy[1] * rs8) |
+        ((unsigned int)cvt2_e4m3(vy[2] * rs8, vy[3] * rs8) << 16);
+  }
+}
+
 // ---- host: kernel selection and launch -------------------------------------
 
 // activation name -> ACT_* code ("" = none); throws on an unknown name
