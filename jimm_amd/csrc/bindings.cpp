@@ -34,6 +34,13 @@ std::vector<torch::Tensor> adam_prepare(std::vector<torch::Tensor> ps,
                                         std::vector<c10::optional<torch::Tensor>> masters);
 void adam_apply(torch::Tensor desc, int64_t nchunks, torch::Tensor lr_dev,
                 torch::Tensor step_dev, double b1, double b2, double eps, double wd);
+std::vector<torch::Tensor> grad_desc_prepare(std::vector<torch::Tensor> gs);
+void grad_sqnorm(torch::Tensor desc, int64_t nchunks, torch::Tensor partials, int64_t offset);
+void clip_finalize(torch::Tensor partials, torch::Tensor stats, double max_norm);
+void adam_apply_clipped(torch::Tensor desc, int64_t nchunks, torch::Tensor lr_dev,
+                        torch::Tensor step_dev, torch::Tensor stats, double b1, double b2,
+                        double eps, double wd);
+void grad_scale(torch::Tensor desc, int64_t nchunks, torch::Tensor stats);
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     bool causal, double scale, std::string path);
 void attn_bwd_p(torch::Tensor s, torch::Tensor lse, bool causal, double scale);
@@ -93,6 +100,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step", &adam_step, "fused multi-tensor Adam (K14)");
   m.def("adam_prepare", &adam_prepare, "build device chunk descriptors once (K14)");
   m.def("adam_apply", &adam_apply, "graph-capturable fused Adam update (K14)");
+  m.def("grad_desc_prepare", &grad_desc_prepare,
+        "chunk descriptors over a bare gradient list (K14 clipping)");
+  m.def("grad_sqnorm", &grad_sqnorm, "per-chunk sum of squares of the gradients (K14 clipping)",
+        py::arg("desc"), py::arg("nchunks"), py::arg("partials"), py::arg("offset") = 0);
+  m.def("clip_finalize", &clip_finalize,
+        "chunk partials -> device stats [norm, coef, finite, skipped] (K14 clipping)");
+  m.def("adam_apply_clipped", &adam_apply_clipped,
+        "adam_apply with g scaled by the device clip coefficient; skips on a non-finite norm");
+  m.def("grad_scale", &grad_scale, "in-place g *= device clip coefficient (K14 clipping)");
   m.def("attn_fwd", &attn_fwd,
         "flash attention forward (K5); path: auto | tiled | resident",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),

@@ -36,6 +36,8 @@ class TrainConfig:
     min_lr: float = 0.0
     # dropout masks are a function of (seed + dp_rank, step, site, element)
     seed: int = 0
+    # global-norm gradient clipping inside the fused Adam step; None = off
+    max_grad_norm: float | None = None
     extra: dict = field(default_factory=dict)
 
 
@@ -47,7 +49,8 @@ class Trainer:
         self.model = model
         self.cfg = cfg
         self.ddp = DataParallelGrads(model, bucket_bytes=cfg.bucket_bytes, process_group=process_group)
-        self.opt = Adam(model.parameters(), lr=cfg.lr, betas=cfg.betas, weight_decay=cfg.weight_decay)
+        self.opt = Adam(model.parameters(), lr=cfg.lr, betas=cfg.betas, weight_decay=cfg.weight_decay,
+                        max_grad_norm=cfg.max_grad_norm)
         self.group = process_group
         self.step_idx = 0
         # every data-parallel rank draws its own dropout masks
@@ -151,6 +154,10 @@ class Trainer:
         self.ddp.finalize()
         self.opt.step()
         self.step_idx += 1
+        if self.cfg.max_grad_norm is not None:
+            # norm of the DP-averaged grads (taken after finalize): the same on
+            # every rank. A view of the device stats buffer, live under replay.
+            out["grad_norm"] = self.opt.last_grad_norm
         out["loss"] = loss.detach()
         return out
 
