@@ -80,6 +80,15 @@ std::vector<torch::Tensor> linear_fwd_actgrad(torch::Tensor x, torch::Tensor w,
 torch::Tensor dropout_fwd(torch::Tensor x, double p, c10::optional<torch::Tensor> rng,
                           int64_t site);
 torch::Tensor gemm_nt_8p_gradmul(torch::Tensor dy, torch::Tensor wt, torch::Tensor g);
+bool sim_supported(int64_t M, int64_t N, int64_t D, std::string dtype);
+std::vector<torch::Tensor> sim_lse_fwd(torch::Tensor a, torch::Tensor b, torch::Tensor scale,
+                                       int64_t diag0);
+torch::Tensor sim_sigmoid_fwd(torch::Tensor a, torch::Tensor b, torch::Tensor scale,
+                              torch::Tensor bias, int64_t diag0);
+std::vector<torch::Tensor> sim_grad(torch::Tensor a, torch::Tensor b, torch::Tensor scale,
+                                    c10::optional<torch::Tensor> bias,
+                                    c10::optional<torch::Tensor> lse, torch::Tensor coef,
+                                    int64_t diag0, int64_t mode);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd, "LayerNorm forward (K3)");
@@ -154,4 +163,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("p"), py::arg("rng"), py::arg("site") = 0);
   m.def("gemm_nt_8p_gradmul", &gemm_nt_8p_gradmul,
         "dX GEMM times a saved fp16 activation derivative");
+  m.def("sim_supported", &sim_supported, "fused similarity-loss kernels: shape / dtype check (K12)");
+  m.def("sim_lse_fwd", &sim_lse_fwd,
+        "softmax-CE over scale * a @ b^T without stored logits -> (lse, pos) (K12)",
+        py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("diag0"));
+  m.def("sim_sigmoid_fwd", &sim_sigmoid_fwd,
+        "SigLIP sigmoid loss sum over scale * a @ b^T + bias without stored logits (K12)",
+        py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("bias"), py::arg("diag0"));
+  m.def("sim_grad", &sim_grad,
+        "logit gradient of one column chunk, recomputed -> (G bf16, dscale, dbias) (K12); "
+        "mode 0 = softmax, 1 = sigmoid",
+        py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("bias"), py::arg("lse"),
+        py::arg("coef"), py::arg("diag0"), py::arg("mode"));
 }

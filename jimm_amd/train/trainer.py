@@ -38,6 +38,8 @@ class TrainConfig:
     seed: int = 0
     # global-norm gradient clipping inside the fused Adam step; None = off
     max_grad_norm: float | None = None
+    # clip / siglip: loss head that never stores the logit block (ops/losses.py)
+    fused_loss_head: bool = False
     extra: dict = field(default_factory=dict)
 
 
@@ -142,12 +144,14 @@ class Trainer:
             images, ids = batch
             img_emb = self.model.encode_image(images)
             txt_emb = self.model.encode_text(ids)
-            loss = L.clip_contrastive_loss(img_emb, txt_emb, self.model.logit_scale, group=self.group)
+            loss = L.clip_contrastive_loss(img_emb, txt_emb, self.model.logit_scale, group=self.group,
+                                           fused=self.cfg.fused_loss_head)
         elif self.cfg.task == "siglip":
             images, ids = batch
             img_emb = self.model.encode_image(images)
             txt_emb = self.model.encode_text(ids)
-            loss = L.siglip_sigmoid_loss(img_emb, txt_emb, self.model.logit_scale, self.model.logit_bias, group=self.group)
+            loss = L.siglip_sigmoid_loss(img_emb, txt_emb, self.model.logit_scale, self.model.logit_bias, group=self.group,
+                                         fused=self.cfg.fused_loss_head)
         else:
             raise ValueError(self.cfg.task)
         loss.backward()

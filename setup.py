@@ -33,6 +33,7 @@ setup(
                 "jimm_amd/csrc/gemm8p.hip",
                 "jimm_amd/csrc/gemm_tn8p.hip",
                 "jimm_amd/csrc/losses.hip",
+                "jimm_amd/csrc/simloss.hip",
                 "jimm_amd/csrc/probe.hip",
             ],
             extra_compile_args={
