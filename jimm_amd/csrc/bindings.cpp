@@ -80,6 +80,12 @@ std::vector<torch::Tensor> linear_fwd_actgrad(torch::Tensor x, torch::Tensor w,
 torch::Tensor dropout_fwd(torch::Tensor x, double p, c10::optional<torch::Tensor> rng,
                           int64_t site);
 torch::Tensor gemm_nt_8p_gradmul(torch::Tensor dy, torch::Tensor wt, torch::Tensor g);
+bool gemm_f8_supported(int64_t M, int64_t N, int64_t K);
+std::vector<torch::Tensor> linear_fwd_f8(torch::Tensor a8, torch::Tensor sa, torch::Tensor b8,
+                                         torch::Tensor sb, c10::optional<torch::Tensor> bias,
+                                         std::string act, c10::optional<torch::Tensor> res,
+                                         bool save_pre, c10::optional<torch::Tensor> scale_out,
+                                         c10::optional<torch::Tensor> amax_out);
 bool sim_supported(int64_t M, int64_t N, int64_t D, std::string dtype);
 std::vector<torch::Tensor> sim_lse_fwd(torch::Tensor a, torch::Tensor b, torch::Tensor scale,
                                        int64_t diag0);
@@ -163,7 +169,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("p"), py::arg("rng"), py::arg("site") = 0);
   m.def("gemm_nt_8p_gradmul", &gemm_nt_8p_gradmul,
         "dX GEMM times a saved fp16 activation derivative");
-  m.def("sim_supported", &sim_supported, "fused similarity-loss kernels: shape / dtype check (K12)");
+  m.def("gemm_f8_supported", &gemm_f8_supported, "e4m3 256-tile GEMM shape check");
+  m.def("linear_fwd_f8", &linear_fwd_f8,
+        "e4m3 MFMA GEMM (16x16x128) + fused epilogue -> [y, z | None, y8 | None]",
+        py::arg("a8"), py::arg("sa"), py::arg("b8"), py::arg("sb"), py::arg("bias") = py::none(),
+        py::arg("act") = "", py::arg("res") = py::none(), py::arg("save_pre") = false,
+        py::arg("scale_out") = py::none(), py::arg("amax_out") = py::none());
+  m.def("sim_supported",&sim_supported, "fused similarity-loss kernels: shape / dtype check (K12)");
   m.def("sim_lse_fwd", &sim_lse_fwd,
         "softmax-CE over scale * a @ b^T without stored logits -> (lse, pos) (K12)",
         py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("diag0"));

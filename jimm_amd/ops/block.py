@@ -31,10 +31,12 @@ from jimm_amd.ops.hip_linear import (
     _FP8_STATE,
     _gemm_mode,
     _quant_e4m3,
+    fp8_hip,
     gemm_dw_db,
     gemm_dx,
     gemm_dx_act,
     gemm_fwd,
+    gemm_fwd_f8,
 )
 from jimm_amd.ops.philox_dropout import dropout_threshold
 
@@ -163,12 +165,19 @@ class EncoderBlockFn(torch.autograd.Function):
         )
         if drop and (fp8 or not hip):
             raise RuntimeError("fused block: dropout runs on the bf16 HIP GEMM path only")
+        # engine of the e4m3 GEMMs, per site: the in-house e4m3 kernel with
+        # its epilogues fused (set_fp8(gemm="hip"), shape permitting), else
+        # scaled_mm + the separate passes
+        M, mlp = B * L, w1.shape[0]
         if fp8:
             amax8.zero_()
             h1, h1q, mean1, rstd1 = ext.layernorm_fwd_fp8(
                 x, ln1w, ln1b, eps, scale8[0:1], amax8[0:1]
             )
-            qkv2 = _mm_fp8q(h1q, scale8[0:1], wqkv, bias=bqkv)
+            if fp8_hip(ext, M, 3 * H, H):
+                qkv2 = gemm_fwd_f8(ext, h1q, scale8[0:1], *_quant_e4m3(wqkv), bqkv)[0]
+            else:
+                qkv2 = _mm_fp8q(h1q, scale8[0:1], wqkv, bias=bqkv)
         else:
             h1, mean1, rstd1 = ext.layernorm_fwd(x, ln1w, ln1b, eps)
             qkv2, _ = gemm_fwd(ext, h1.view(-1, H), wqkv, bqkv, None, None, hip=hip)  # (M, 3H)
@@ -181,9 +190,17 @@ class EncoderBlockFn(torch.autograd.Function):
             h2, h2q, mean2, rstd2 = ext.layernorm_fwd_fp8(
                 a3, ln2w, ln2b, eps, scale8[1:2], amax8[1:2]
             )
-            z1 = _mm_fp8q(h2q, scale8[1:2], w1, bias=b1)  # z1 = pre-act (bias fused)
-            f, f8 = ext.bias_act_fwd_fp8(z1, None, act, scale8[2:3], amax8[2:3])
-            y = ext.bias_act_fwd(_mm_fp8q(f8, scale8[2:3], w2, bias=b2), None, "", a)
+            if fp8_hip(ext, M, mlp, H) and b1 is not None and act:
+                # one launch: bias + act, z1 saved, f emitted as e4m3
+                f, z1, f8 = gemm_fwd_f8(ext, h2q, scale8[1:2], *_quant_e4m3(w1), b1, act,
+                                        None, scale8[2:3], amax8[2:3])
+            else:
+                z1 = _mm_fp8q(h2q, scale8[1:2], w1, bias=b1)  # z1 = pre-act (bias fused)
+                f, f8 = ext.bias_act_fwd_fp8(z1, None, act, scale8[2:3], amax8[2:3])
+            if fp8_hip(ext, M, H, mlp):
+                y = gemm_fwd_f8(ext, f8, scale8[2:3], *_quant_e4m3(w2), b2, None, a)[0]
+            else:
+                y = ext.bias_act_fwd(_mm_fp8q(f8, scale8[2:3], w2, bias=b2), None, "", a)
             # next step's forward scales (delayed); grad sites [3:5] are
             # updated at backward end, after their amax is collected
             scale8[0:3].copy_(torch.clamp(amax8[0:3] / 448.0, min=1e-12))
@@ -245,10 +262,13 @@ class EncoderBlockFn(torch.autograd.Function):
         dw2, db2 = gemm_dw_db(ext, dyd, f, w2.dtype)
         if fp8:
             w1t8, sw1 = _quant_e4m3(w1, transpose=True)
-            dh2 = torch._scaled_mm(
-                dz18.view(torch.float8_e4m3fn), w1t8.t(), scale_a=scale8[3:4].view(1, 1),
-                scale_b=sw1.view(1, 1), out_dtype=torch.bfloat16,
-            )
+            if fp8_hip(ext, dz18.shape[0], H, w1.shape[0]):
+                dh2 = gemm_fwd_f8(ext, dz18, scale8[3:4], w1t8, sw1)[0]
+            else:
+                dh2 = torch._scaled_mm(
+                    dz18.view(torch.float8_e4m3fn), w1t8.t(), scale_a=scale8[3:4].view(1, 1),
+                    scale_b=sw1.view(1, 1), out_dtype=torch.bfloat16,
+                )
         else:
             dh2 = gemm_dx(ext, dz1, w1)
         dw1, db1 = gemm_dw_db(ext, dz1, h2_2, w1.dtype)

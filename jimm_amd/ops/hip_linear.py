@@ -22,7 +22,11 @@ own rule: ``JIMM_AMD_GEMM`` (``hip``, the default, or ``blas``; read by
 fp8 (``jimm_amd.ops.set_fp8(True)``): e4m3 scaled_mm forward GEMMs with
 per-tensor dynamic device-side scales (graph-capturable); the backward GEMMs,
 LN and losses stay bf16/fp32. The fused block has its own producer-fused
-fp8 arm (ops/block.py).
+fp8 arm (ops/block.py). ``set_fp8(True, gemm="hip")`` (or
+``JIMM_AMD_FP8_GEMM=hip``; default ``blas``) runs those e4m3 GEMMs on the
+in-house 16x16x128 MFMA kernel (csrc/gemm8p_f8.hip) with the bias /
+activation / residual / e4m3-emission epilogues fused in, where
+``ext.gemm_f8_supported`` takes the shape (``gemm_fwd_f8`` below).
 """
 
 from __future__ import annotations
@@ -42,12 +46,19 @@ from jimm_amd.ops import _backend
 # bf16/fp32 throughout. Enable with jimm_amd.ops.set_fp8(True).
 # ---------------------------------------------------------------------------
 
-_FP8_STATE = {"enabled": False}
+_FP8_STATE = {"enabled": False, "gemm": None}
 _FP8_MAX = 448.0  # e4m3 (OCP) max normal
 
 
-def set_fp8(on: bool = True) -> None:
+def set_fp8(on: bool = True, gemm: str | None = None) -> None:
+    """Switch the e4m3 forward path. gemm: the engine of its GEMMs, "blas"
+    (torch._scaled_mm + separate epilogue passes) or "hip" (the in-house e4m3
+    MFMA kernel, epilogues fused); None leaves the choice to
+    JIMM_AMD_FP8_GEMM (default blas)."""
+    if gemm not in (None, "blas", "hip"):
+        raise ValueError(f"set_fp8: gemm must be 'blas' or 'hip', got {gemm!r}")
     _FP8_STATE["enabled"] = bool(on)
+    _FP8_STATE["gemm"] = gemm
 
 
 def fp8_enabled() -> bool:
@@ -87,6 +98,12 @@ def _gemm_mode() -> str:
     return os.environ.get("JIMM_AMD_GEMM", "hip")
 
 
+def _fp8_gemm_mode() -> str:
+    # engine of the e4m3 GEMMs under set_fp8: its gemm= argument, else
+    # JIMM_AMD_FP8_GEMM ("blas", the default, or "hip").
+    return _FP8_STATE["gemm"] or os.environ.get("JIMM_AMD_FP8_GEMM", "blas")
+
+
 def _deterministic() -> bool:
     return os.environ.get("JIMM_AMD_DETERMINISTIC", "0") == "1"
 
@@ -120,6 +137,20 @@ def gemm_fwd(ext, x2, w, b, act, res2, *, hip: bool, save=None, drop=None):
     # pre-activation (z+bias); y aliases z when there is no act.
     y = ext.bias_act_fwd(z, b, act, res2)
     return y, (z if save else None)
+
+
+def fp8_hip(ext, M: int, N: int, K: int) -> bool:
+    """True when an (M, K) x (N, K)^T e4m3 GEMM runs on the in-house kernel."""
+    return _fp8_gemm_mode() == "hip" and ext.gemm_f8_supported(M, N, K)
+
+
+def gemm_fwd_f8(ext, a8, sa, w8, sw, b=None, act=None, res2=None, scale_out=None, amax_out=None):
+    """y = act((sa*sw) * a8 @ w8^T + b) [+ res2] on e4m3 bytes with device
+    scales, one launch of the in-house e4m3 kernel -> (y, z, y8): z the bf16
+    pre-activation (saved exactly when there is an activation), y8 the e4m3
+    copy of y under scale_out with its amax folded into amax_out (fc1 form:
+    activation + bias, no residual). The caller has checked fp8_hip."""
+    return ext.linear_fwd_f8(a8, sa, w8, sw, b, act or "", res2, bool(act), scale_out, amax_out)
 
 
 def gemm_dx(ext, dz: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -194,8 +225,11 @@ class _LinearActFn(torch.autograd.Function):
         res2 = residual.contiguous().reshape(-1, out_f) if residual is not None else None
         ext = _backend.ext()
         if _FP8_STATE["enabled"] and _fp8_ok(x2, w):
-            z = _gemm_nt_fp8(x2, w)
-            y = ext.bias_act_fwd(z, b, act or "", res2)
+            if fp8_hip(ext, x2.shape[0], out_f, in_f):
+                y, z, _ = gemm_fwd_f8(ext, *_quant_e4m3(x2), *_quant_e4m3(w), b, act, res2)
+            else:
+                z = _gemm_nt_fp8(x2, w)
+                y = ext.bias_act_fwd(z, b, act or "", res2)
         else:
             hip = _gemm_mode() == "hip" and ext.gemm_supported(x2.shape[0], out_f, in_f, str(x2.dtype))
             y, z = gemm_fwd(ext, x2, w, b, act, res2, hip=hip, save="z" if act is not None else None)
