@@ -31,6 +31,9 @@
 //         barrier BA(u); 16 MFMA
 //   B(u): tr-read dz frags (pr1); lgkmcnt(0); counted vmcnt; barrier
 //         BB(u); issue unit u+RING into slot(u); 16 MFMA
+// (Issuing a phase's reads one phase ahead, under the wave's own MFMAs,
+// measured 1-4% slower on every ViT-B shape and was not kept;
+// profiles/dw_readahead_NOTES.md section 4.)
 // Certification:
 //   RAW  unit v is first read in A(v), after barrier BB(v-1).  Before
 //        arriving at BB(v-1) every wave waits until its own pieces of v
@@ -55,6 +58,15 @@
 // 0/1, one barrier, then the same two-phase walk.  M-tail rows load zeros
 // (no clamping — this is an accumulation).
 //
+// Bias fold (DBOUT): db[n] = sum_m dz[m][n] comes out of the dz fragments
+// already in registers.  The four waves of equal wm hold the same dz
+// fragments and the nt_k workgroups of one (n-tile, split) see the same dz,
+// so the work is dealt out: wave (wm, wn) folds fragment mi = wn only, and
+// of the chunk's 32-row units (ring units, then the tail's two) workgroup
+// k-tile kt folds those with unit % P == kt, P = min(nt_k, FOLD_PMAX);
+// k-tiles >= P fold nothing.  Each unit of each chunk is counted once; at
+// the end a folding wave adds its 2 x 16 columns with one atomic each.
+//
 // Split-M: grid.y walks m-chunks (slow index -> the chunk's operand rows
 // stay L3-resident across its output tiles).  Each split writes a private
 // fp32 slice of a workspace and ws_reduce_kernel folds them in fixed order
@@ -63,6 +75,8 @@
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+
+#include <climits>
 
 #include "mfma.h"
 
@@ -79,6 +93,7 @@ constexpr int UNIT_BYTES = 16384;   // one operand's 32x256 bf16 unit image
 constexpr int SLOT_BYTES = 2 * UNIT_BYTES;  // dz image + X image
 constexpr int RING = 5;             // ring slots (RING * 32 KiB of LDS)
 constexpr int GLDS_PER_UNIT = 4;    // per thread: 2 dz + 2 X
+constexpr int FOLD_PMAX = 4;        // k-tiles of one n-tile that share the bias fold
 
 // Counted wait: returns once at most the `newer` most recently issued
 // units of this wave are still in flight (vmcnt retires glds in order).
@@ -139,11 +154,30 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
 
   f32x4_t acc[2][4][4] = {};  // [pr][mi][ni]
   // DBOUT: db[n] = sum_m dz[m][n] folded out of the A fragments already in
-  // registers (the separate colsum kernel re-reads dz from HBM). Only the
-  // k0==0 / wn==0 waves contribute (the same dz fragments are read by every
-  // k-tile and every wn), so the whole-M coverage comes from the k0==0
-  // column of workgroups across splits.
-  float db_acc[2][4] = {};
+  // registers (the separate colsum kernel re-reads dz from HBM), dealt out
+  // over waves and k-tiles (header): this wave folds fragment mi = wn of the
+  // units fold_at, fold_at + fold_p, ...; k-tiles >= fold_p never fold.
+  float db_acc[2] = {};
+  const int wn_u = __builtin_amdgcn_readfirstlane(wn);  // scalar, for the switch
+  const int kt = wg % nt_k;
+  const int fold_p = nt_k < FOLD_PMAX ? nt_k : FOLD_PMAX;
+  int fold_at = kt < fold_p ? kt : INT_MAX;  // next unit of the chunk to fold
+  int unit_no = 0;                           // ring units, then the tail's two
+  // sum of one fragment's 8 dz values (this lane's column, 8 rows)
+  auto sum8 = [](const bf16x8_t& a) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += __uint_as_float((unsigned int)(unsigned short)a[j] << 16);
+    return s;
+  };
+  auto fold = [&](const bf16x8_t (&ad)[4], int pr) __attribute__((always_inline)) {
+    switch (wn_u) {
+      case 0: db_acc[pr] += sum8(ad[0]); break;
+      case 1: db_acc[pr] += sum8(ad[1]); break;
+      case 2: db_acc[pr] += sum8(ad[2]); break;
+      default: db_acc[pr] += sum8(ad[3]); break;
+    }
+  };
 
   // Ring staging for this thread: glds with the image permutation on the
   // per-lane SOURCE address — piece j of a unit covers unit-image bytes
@@ -207,6 +241,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
                           auto&& after_bb) __attribute__((always_inline)) {
     typedef const __attribute__((address_space(3))) char* lds_p;
     bf16x8_t xb[4];  // X-side fragments, reused across the pr pair
+    bool do_fold = false;
+    if (DBOUT) {
+      do_fold = unit_no == fold_at;
+      if (do_fold) fold_at += fold_p;
+      ++unit_no;
+    }
     // ---------- phase A (pr=0) ----------
     {
       // B (X image) frags ni=0..3 at nt = wn*4+ni, plus A (dz) frags
@@ -249,16 +289,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
       ad[1] = __builtin_shufflevector(a1l, a1h, 0, 1, 2, 3, 4, 5, 6, 7);
       ad[2] = __builtin_shufflevector(a2l, a2h, 0, 1, 2, 3, 4, 5, 6, 7);
       ad[3] = __builtin_shufflevector(a3l, a3h, 0, 1, 2, 3, 4, 5, 6, 7);
-      if (DBOUT && wn == 0 && k0 == 0) {
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
-          const bf16* av = reinterpret_cast<const bf16*>(&ad[mi]);
-          float s8 = 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) s8 += bf2f(av[j]);
-          db_acc[0][mi] += s8;
-        }
-      }
+      if (DBOUT && do_fold) fold(ad, 0);
       raw_barrier();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -292,16 +323,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
       ad[1] = __builtin_shufflevector(a1l, a1h, 0, 1, 2, 3, 4, 5, 6, 7);
       ad[2] = __builtin_shufflevector(a2l, a2h, 0, 1, 2, 3, 4, 5, 6, 7);
       ad[3] = __builtin_shufflevector(a3l, a3h, 0, 1, 2, 3, 4, 5, 6, 7);
-      if (DBOUT && wn == 0 && k0 == 0) {
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
-          const bf16* av = reinterpret_cast<const bf16*>(&ad[mi]);
-          float s8 = 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) s8 += bf2f(av[j]);
-          db_acc[1][mi] += s8;
-        }
-      }
+      if (DBOUT && do_fold) fold(ad, 1);
       before_bb();
       raw_barrier();
       after_bb();
@@ -347,19 +369,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
       consume_unit(smem + kh * SLOT_BYTES, [] {}, [] {});
   }
 
-  if (DBOUT && wn == 0 && k0 == 0) {
-    // A-frag row for lane = lo: db_acc[pr][mi] covers n = n0 + pr*128 +
-    // wm*64 + 16*mi + lo over this wave's m chunks (hi groups); reduce
-    // over hi, one atomic per n per split
+  if (DBOUT && kt < fold_p) {
+    // A-frag row for lane = lo: db_acc[pr] covers n = n0 + pr*128 + wm*64 +
+    // 16*wn + lo over the 8-row groups (hi) of the units this wave folded;
+    // reduce over hi, one atomic per n per folding k-tile per split
 #pragma unroll
-    for (int pr = 0; pr < 2; ++pr)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-        float v_ = db_acc[pr][mi];
-        v_ += __shfl_xor(v_, 16, WAVE);
-        v_ += __shfl_xor(v_, 32, WAVE);
-        if (hi == 0) atomicAdd(DB + n0 + pr * 128 + wm * 64 + 16 * mi + lo, v_);
-      }
+    for (int pr = 0; pr < 2; ++pr) {
+      float v_ = db_acc[pr];
+      v_ += __shfl_xor(v_, 16, WAVE);
+      v_ += __shfl_xor(v_, 32, WAVE);
+      if (hi == 0) atomicAdd(DB + n0 + pr * 128 + wm * 64 + 16 * wn + lo, v_);
+    }
   }
 
   // Epilogue: acc[pr][mi][ni] -> C rows n = n0 + pr*128 + wm*64 + 16mi +

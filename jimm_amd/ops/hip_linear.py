@@ -304,8 +304,10 @@ class _PatchEmbedFn(torch.autograd.Function):
         patch = ctx.patch
         ext = _backend.ext()
         dy2 = dy.contiguous().reshape(-1, dy.shape[-1])
-        dcols = gemm_dx(ext, dy2, w2)
-        dimg = ext.col2im_patch(dcols, list(ctx.img_shape), patch) if ctx.needs_input_grad[0] else None
+        dimg = None
+        if ctx.needs_input_grad[0]:
+            dcols = gemm_dx(ext, dy2, w2)
+            dimg = ext.col2im_patch(dcols, list(ctx.img_shape), patch)
         # dW alone, db by the separate colsum: this path does not use the
         # TN kernel's db fold
         dw, _ = gemm_dw_db(ext, dy2, cols, w2.dtype, ctx.needs_input_grad[1], need_db=False)
