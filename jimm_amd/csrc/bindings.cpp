@@ -64,6 +64,10 @@ int64_t gemm_tn8p_choose_splitm(int64_t M, int64_t tiles, int64_t cus);
 torch::Tensor gemm_tn_8p(torch::Tensor dz, torch::Tensor x, int64_t splitm, bool out_bf16);
 std::vector<torch::Tensor> gemm_tn_8p_db(torch::Tensor dz, torch::Tensor x, int64_t splitm,
                                          bool out_bf16);
+bool gemm_tn_128_supported(int64_t M, int64_t N, int64_t K);
+torch::Tensor gemm_tn_128(torch::Tensor dz, torch::Tensor x, int64_t splitm, bool out_bf16);
+std::vector<torch::Tensor> gemm_tn_128_db(torch::Tensor dz, torch::Tensor x, int64_t splitm,
+                                          bool out_bf16);
 torch::Tensor gemm_nt_8p_gradact(torch::Tensor dy, torch::Tensor wt, torch::Tensor z, std::string act);
 torch::Tensor tr16_probe(torch::Tensor src, int64_t mode);
 std::vector<torch::Tensor> linear_fwd(torch::Tensor x, torch::Tensor w,
@@ -146,6 +150,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_tn_8p", &gemm_tn_8p, "TN weight-grad GEMM, split-M, tr_b16 (K15)",
         py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false);
   m.def("gemm_tn_8p_db", &gemm_tn_8p_db, "split-M TN dW with fused bias-grad colsum",
+        py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false);
+  m.def("gemm_tn_128_supported", &gemm_tn_128_supported,
+        "128-tile TN dW GEMM shape check (N, K multiples of 8)");
+  m.def("gemm_tn_128", &gemm_tn_128, "TN weight-grad GEMM, 128x128 tiles, ragged N / K, split-M",
+        py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false);
+  m.def("gemm_tn_128_db", &gemm_tn_128_db, "128-tile TN dW with fused bias-grad colsum",
         py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false);
   m.def("gemm_nt_8p_gradact", &gemm_nt_8p_gradact, "dX GEMM with fused act-backward epilogue");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 lane-mapping probe");

@@ -467,6 +467,20 @@ int64_t gemm_tn8p_choose_splitm(int64_t M, int64_t tiles, int64_t cus) {
   return smax;
 }
 
+// out[i] = sum over `splits` fp32 slices of n elements each (n % 4 == 0), in
+// fixed order, as fp32 or rounded once to bf16. Shared with gemm_tn128.hip.
+void tn_ws_reduce(const float* ws, void* out, int64_t n, int splits, bool out_bf16,
+                  hipStream_t stream) {
+  const int block = 256;
+  const int grid = (int)std::min<int64_t>((n / 4 + block - 1) / block, 8192);
+  if (out_bf16)
+    hipLaunchKernelGGL(ws_reduce_kernel<true>, dim3(grid), dim3(block), 0, stream, ws, out, n,
+                       splits);
+  else
+    hipLaunchKernelGGL(ws_reduce_kernel<false>, dim3(grid), dim3(block), 0, stream, ws, out, n,
+                       splits);
+}
+
 static torch::Tensor tn8p_run(torch::Tensor dz, torch::Tensor x, float* dbp, int64_t splitm_arg,
                               bool out_bf16) {
   // dz (M, N) bf16, x (M, Kw) bf16 -> dW (N, Kw) = dz^T @ x, fp32 or
@@ -523,15 +537,7 @@ static torch::Tensor tn8p_run(torch::Tensor dz, torch::Tensor x, float* dbp, int
   if (dbp) LAUNCH_TN(true, true);
   else LAUNCH_TN(false, true);
 #undef LAUNCH_TN
-  const int64_t n = (int64_t)N * Kw;
-  const int block = 256;
-  const int grid = (int)std::min<int64_t>((n / 4 + block - 1) / block, 8192);
-  if (out_bf16)
-    hipLaunchKernelGGL(ws_reduce_kernel<true>, dim3(grid), dim3(block), 0, stream,
-                       ws.data_ptr<float>(), C.data_ptr(), n, splitm);
-  else
-    hipLaunchKernelGGL(ws_reduce_kernel<false>, dim3(grid), dim3(block), 0, stream,
-                       ws.data_ptr<float>(), C.data_ptr(), n, splitm);
+  tn_ws_reduce(ws.data_ptr<float>(), C.data_ptr(), (int64_t)N * Kw, splitm, out_bf16, stream);
   return C;
 }
 

@@ -7,8 +7,12 @@ Two engines run a GEMM:
     N % 256 == 0, K % 64 == 0 and K >= 128, else the 128-tile kernels of
     csrc/gemm.hip for any K % 64 == 0), with the bias / activation / residual /
     dropout epilogues and the activation backward fused into the GEMM; dW on
-    the split-M TN kernel (csrc/gemm_tn8p.hip, fp32 accumulate, N % 256 == 0
-    and K % 256 == 0), which can fold the bias gradient out of its operands;
+    the split-M TN kernels (fp32 accumulate), which can fold the bias
+    gradient out of their operands: the 256-tile kernel of csrc/gemm_tn8p.hip
+    where N % 256 == 0 and K % 256 == 0, else the 128-tile kernel of
+    csrc/gemm_tn128.hip for any N % 8 == 0, K % 8 == 0 with M >= 256 and at
+    most 162 output tiles of 128 x 128, 243 with the bias fold (ViT-S,
+    so400m's proj and qkv, class heads); every other dW goes to torch.matmul;
   * hipBLASLt/rocBLAS through torch (with the committed MI355X TunableOp
     table) + the separate fused bias+act(+residual) elementwise kernel.
 
@@ -191,25 +195,59 @@ def _colsum(ext, dz: torch.Tensor) -> torch.Tensor:
     return dz.sum(dim=0)
 
 
+# Fewest rows at which an off-grid dW goes to the 128-tile TN kernel: below
+# four 64-row m-steps the call is launch-bound on either engine.
+_TN128_MIN_M = 256
+# Most 128x128 output tiles at which it does: with more, rocBLAS fills the
+# device with larger tiles and is ahead (measured crossover at M = 46656:
+# between 162 and 192 tiles for dW alone, beyond 243 and before 306 with the
+# bias fold, which saves the separate colsum pass;
+# profiles/dw_offgrid_NOTES.md).
+_TN128_MAX_TILES = 162
+_TN128_MAX_TILES_DB = 243
+
+
+def _tn128_ok(ext, dz, x2, fold: bool) -> bool:
+    """Whether an off-grid dW runs the 128-tile TN kernel: its domain (N and
+    K multiples of 8, contiguous 16-byte-aligned bf16 operands) and the two
+    routing conditions above. fold: the call will use the bias fold."""
+    M, N, K = dz.shape[0], dz.shape[1], x2.shape[1]
+    return (
+        M >= _TN128_MIN_M
+        and ext.gemm_tn_128_supported(M, N, K)
+        and -(-N // 128) * -(-K // 128) <= (_TN128_MAX_TILES_DB if fold else _TN128_MAX_TILES)
+        and x2.dtype == torch.bfloat16
+        and dz.is_contiguous()
+        and x2.is_contiguous()
+        and dz.data_ptr() % 16 == 0
+        and x2.data_ptr() % 16 == 0
+    )
+
+
 def gemm_dw_db(ext, dz, x2, out_dtype, need_dw: bool = True, need_db: bool = True):
     """(dW = dz^T @ x2 | None, db = colsum(dz) | None). The in-house split-M
-    TN kernel (fp32 accumulate, deterministic fixed-order combine of the
+    TN kernels (fp32 accumulate, deterministic fixed-order combine of the
     splits; bf16 weights: the combine rounds to bf16 itself, no cast pass)
-    folds db out of the dz fragments it already holds in registers instead
+    fold db out of the dz fragments they already hold in registers instead
     of a separate full re-read of dz. That fold adds fp32 atomically, so
-    deterministic mode does not take it."""
-    tn = (
-        need_dw
-        and _gemm_mode() == "hip"
-        and dz.dtype == torch.bfloat16
-        and ext.gemm_tn8p_supported(dz.shape[0], dz.shape[1], x2.shape[1])
-    )
-    if tn and need_db and not _deterministic():
-        dw, db = ext.gemm_tn_8p_db(dz, x2, 0, out_dtype == torch.bfloat16)
+    deterministic mode does not take it. Shapes on the 256 grid run the
+    256-tile kernel; any other N % 8 == 0, K % 8 == 0 shape with M >= 256 and
+    few enough output tiles the 128-tile kernel; the rest torch.matmul +
+    colsum."""
+    tn = need_dw and _gemm_mode() == "hip" and dz.dtype == torch.bfloat16
+    fold = need_db and not _deterministic()
+    if tn and ext.gemm_tn8p_supported(dz.shape[0], dz.shape[1], x2.shape[1]):
+        tn_dw, tn_dw_db = ext.gemm_tn_8p, ext.gemm_tn_8p_db
+    elif tn and _tn128_ok(ext, dz, x2, fold):
+        tn_dw, tn_dw_db = ext.gemm_tn_128, ext.gemm_tn_128_db
+    else:
+        tn = False
+    if tn and fold:
+        dw, db = tn_dw_db(dz, x2, 0, out_dtype == torch.bfloat16)
         return dw.to(out_dtype), db.to(dz.dtype)
     dw = db = None
     if tn and not need_db:
-        dw = ext.gemm_tn_8p(dz, x2, 0, out_dtype == torch.bfloat16).to(out_dtype)
+        dw = tn_dw(dz, x2, 0, out_dtype == torch.bfloat16).to(out_dtype)
     elif need_dw:
         dw = torch.matmul(dz.t(), x2)
     if need_db:
