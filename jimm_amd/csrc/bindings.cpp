@@ -69,6 +69,13 @@ torch::Tensor gemm_tn_128(torch::Tensor dz, torch::Tensor x, int64_t splitm, boo
 std::vector<torch::Tensor> gemm_tn_128_db(torch::Tensor dz, torch::Tensor x, int64_t splitm,
                                           bool out_bf16);
 torch::Tensor gemm_nt_8p_gradact(torch::Tensor dy, torch::Tensor wt, torch::Tensor z, std::string act);
+bool gemm_nt_128_supported(int64_t M, int64_t N, int64_t K);
+std::vector<torch::Tensor> gemm_nt_128(torch::Tensor x, torch::Tensor w,
+                                       c10::optional<torch::Tensor> bias, std::string act,
+                                       c10::optional<torch::Tensor> residual, std::string save);
+torch::Tensor gemm_nt_128_gradmul(torch::Tensor dy, torch::Tensor wt, torch::Tensor g);
+torch::Tensor gemm_nt_128_gradact(torch::Tensor dy, torch::Tensor wt, torch::Tensor z,
+                                  std::string act);
 torch::Tensor tr16_probe(torch::Tensor src, int64_t mode);
 std::vector<torch::Tensor> linear_fwd(torch::Tensor x, torch::Tensor w,
                                       c10::optional<torch::Tensor> bias, std::string act,
@@ -158,6 +165,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_tn_128_db", &gemm_tn_128_db, "128-tile TN dW with fused bias-grad colsum",
         py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false);
   m.def("gemm_nt_8p_gradact", &gemm_nt_8p_gradact, "dX GEMM with fused act-backward epilogue");
+  m.def("gemm_nt_128_supported", &gemm_nt_128_supported,
+        "128-tile NT GEMM shape check (N, K multiples of 8)");
+  m.def("gemm_nt_128", &gemm_nt_128,
+        "NT GEMM, 128x128 tiles, ragged M / N / K, fused epilogue -> (y, z | None); "
+        "save: none | pre | grad",
+        py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("act") = "",
+        py::arg("residual") = py::none(), py::arg("save") = "none");
+  m.def("gemm_nt_128_gradmul", &gemm_nt_128_gradmul,
+        "128-tile dX GEMM times a saved fp16 activation derivative");
+  m.def("gemm_nt_128_gradact", &gemm_nt_128_gradact,
+        "128-tile dX GEMM with fused act-backward epilogue");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 lane-mapping probe");
   m.def("l2norm_fwd", &l2norm_fwd, "row L2-normalize forward (K12)");
   m.def("l2norm_bwd", &l2norm_bwd, "row L2-normalize backward (K12)");

@@ -29,6 +29,7 @@ from jimm_amd.ops import _backend
 from jimm_amd.ops.functional import _split_heads
 from jimm_amd.ops.hip_linear import (
     _FP8_STATE,
+    _nt128_ok,
     _gemm_mode,
     _quant_e4m3,
     fp8_hip,
@@ -37,17 +38,42 @@ from jimm_amd.ops.hip_linear import (
     gemm_dx_act,
     gemm_fwd,
     gemm_fwd_f8,
+    nt128_rows_k_ok,
 )
 from jimm_amd.ops.philox_dropout import dropout_threshold
 
 
-def _hip_gemms(H: int, mlp_dim: int) -> bool:
+def _grid_widths(H: int, mlp_dim: int) -> bool:
+    """Widths whose block GEMMs the kernels behind ``ext.linear_fwd`` take."""
+    return H % 256 == 0 and mlp_dim % 64 == 0
+
+
+def _hip_gemms(H: int, mlp_dim: int, M: int = 0, fp8: bool = False) -> bool:
     """True when the encoder block's forward GEMMs run on the in-house MFMA
-    kernels (JIMM_AMD_GEMM=hip, the default): H % 256 == 0 puts qkv, proj and
-    fc2 (N = 3H, H, H) on the 8-phase kernel, and every K (H or mlp_dim)
-    must be a multiple of 64 for any of them. fc1 (N = mlp_dim) takes the
-    128-tile kernels where mlp_dim % 256 != 0."""
-    return _gemm_mode() == "hip" and H % 256 == 0 and mlp_dim % 64 == 0
+    kernels (JIMM_AMD_GEMM=hip, the default). Two arms:
+      * H % 256 == 0 puts qkv, proj and fc2 (N = 3H, H, H) on the 8-phase
+        kernel, and every K (H or mlp_dim) must be a multiple of 64 for any
+        of them. fc1 (N = mlp_dim) takes the 128-tile kernels of gemm.hip
+        where mlp_dim % 256 != 0;
+      * any other widths that are multiples of 8 with H within the K cap and
+        M rows at or above the floor of the 128-tile NT kernel (ViT-S 384 /
+        1536, ViT-Ti 192 / 768): each GEMM runs the 8-phase kernel where that
+        takes its shape, csrc/gemm_nt128.hip where _nt128_ok admits it (qkv,
+        proj; not fc2, whose K = mlp_dim is beyond the cap) and rocBLAS
+        otherwise. so400m (H = 1152) is beyond the cap. Not with the
+        block's fp8 state on (fp8): its backward arm hands fc2-dX to the
+        8-phase e4m3-emitting kernel, which takes no off-grid shape.
+        Deliberately not routed: at K = 384 (ViT-S qkv and proj forward) the
+        two-buffer kernel behind linear_fwd measured 16-24% ahead of
+        gemm_nt128.hip, which in turn is 1.4-2x ahead of it at K = 192 and
+        576 and wherever M or N is ragged. One width's crossover against a
+        kernel that is due to be retired is left to that follow-up
+        (profiles/nt_offgrid_NOTES.md)."""
+    if _gemm_mode() != "hip":
+        return False
+    return _grid_widths(H, mlp_dim) or (
+        not fp8 and H % 8 == 0 and mlp_dim % 8 == 0 and nt128_rows_k_ok(M, H)
+    )
 
 
 def _act_save_g() -> bool:
@@ -132,7 +158,11 @@ class EncoderBlockFn(torch.autograd.Function):
         # the engine of every bf16 GEMM below: the in-house MFMA kernels with
         # the bias / act / residual epilogues fused into the GEMM kernel
         # itself, or rocBLAS + the fused elementwise pass (gemm_fwd)
-        hip = _hip_gemms(H, w1.shape[0])
+        hip = _hip_gemms(H, w1.shape[0], B * L, scale8 is not None)
+        # the off-grid arm: what the 8-phase kernel does not take runs the
+        # 128-tile NT kernel or rocBLAS instead of the kernels behind
+        # linear_fwd (gemm_fwd)
+        nt128 = hip and not _grid_widths(H, w1.shape[0])
         # active dropout: site0 after the activation, site0 + 1 after fc2,
         # both under the {seed, step} snapshot rng (fused_block_enabled has
         # checked that the bf16 HIP save-g path below takes these shapes)
@@ -180,11 +210,12 @@ class EncoderBlockFn(torch.autograd.Function):
                 qkv2 = _mm_fp8q(h1q, scale8[0:1], wqkv, bias=bqkv)
         else:
             h1, mean1, rstd1 = ext.layernorm_fwd(x, ln1w, ln1b, eps)
-            qkv2, _ = gemm_fwd(ext, h1.view(-1, H), wqkv, bqkv, None, None, hip=hip)  # (M, 3H)
+            qkv2, _ = gemm_fwd(ext, h1.view(-1, H), wqkv, bqkv, None, None, hip=hip,
+                              nt128=nt128)  # (M, 3H)
         qkv = qkv2.view(B, L, 3, num_heads, H // num_heads)
         o, lse = ext.attn_fwd(*_split_heads(qkv), causal, scale)  # (B,nh,L,d), (B,L,nh,d) storage
         o2 = o.transpose(1, 2).reshape(-1, H)                    # free view
-        a, _ = gemm_fwd(ext, o2, wproj, bproj, None, x2, hip=hip)  # + bias + residual
+        a, _ = gemm_fwd(ext, o2, wproj, bproj, None, x2, hip=hip, nt128=nt128)  # + bias + residual
         a3 = a.view(B, L, H)
         if fp8:
             h2, h2q, mean2, rstd2 = ext.layernorm_fwd_fp8(
@@ -206,24 +237,29 @@ class EncoderBlockFn(torch.autograd.Function):
             scale8[0:3].copy_(torch.clamp(amax8[0:3] / 448.0, min=1e-12))
         else:
             h2, mean2, rstd2 = ext.layernorm_fwd(a3, ln2w, ln2b, eps)
-            # fc2-dX runs as (M, mlp, H); where the 8-phase kernel takes it,
-            # z1 holds the fp16 derivative act'(pre) instead of the
-            # pre-activation (nothing else reads z1)
-            save_g = hip and _act_save_g() and ext.gemm8p_supported(B * L, w1.shape[0], H)
+            # fc2-dX runs as (M, mlp, H), the shape of fc1 itself; where a
+            # kernel with the saved-derivative forms takes it (the 8-phase
+            # one, or in the off-grid arm the 128-tile one), z1 holds the fp16
+            # derivative act'(pre) instead of the pre-activation (nothing else
+            # reads z1)
+            save_g = hip and _act_save_g() and (
+                ext.gemm8p_supported(B * L, w1.shape[0], H)
+                or (nt128 and _nt128_ok(ext, h2.view(-1, H), w1, w1.shape[0])))
             if drop and not save_g:
                 raise RuntimeError("fused block: dropout needs the saved-derivative fc1 path")
             # with dropout f = act(z)*m*s and z1 = act'(z)*m*s: the mask of
             # site0 reaches the backward inside the saved derivative
-            f, z1 = gemm_fwd(ext, h2.view(-1, H), w1, b1, act, None, hip=hip,
+            f, z1 = gemm_fwd(ext, h2.view(-1, H), w1, b1, act, None, hip=hip, nt128=nt128,
                              save="g" if save_g else "z", drop=(p, rng, site0) if drop else None)
             # y = a + m*s*(f @ w2^T + b2) at site0 + 1
-            y, _ = gemm_fwd(ext, f, w2, b2, None, a, hip=hip,
+            y, _ = gemm_fwd(ext, f, w2, b2, None, a, hip=hip, nt128=nt128,
                             drop=(p, rng, site0 + 1) if drop else None)
         ctx.save_for_backward(x, ln1w, wqkv, wproj, ln2w, w1, w2,
                               h1, qkv, o, lse, a, mean1, rstd1, mean2, rstd2, h2, z1, f, rng)
         ctx.dims = (B, L, H, num_heads)
         ctx.meta = (act, causal, scale)
         ctx.drop = (p, site0)
+        ctx.hip = hip
         ctx.fp8_state = (scale8, amax8) if fp8 else None
         return y.view(B, L, H)
 
@@ -242,7 +278,7 @@ class EncoderBlockFn(torch.autograd.Function):
         dyd = ext.dropout_fwd(dy2, p, rng, site0 + 1) if rng is not None else dy2
         h1_2 = h1.view(-1, H)
         h2_2 = h2.view(-1, H)
-        hip = _hip_gemms(H, w1.shape[0])
+        hip = ctx.hip  # the forward's engine (the off-grid arm depends on M and fp8)
         fp8 = ctx.fp8_state is not None and hip
 
         # MLP fc2 (+residual into a)

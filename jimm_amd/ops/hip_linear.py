@@ -6,7 +6,11 @@ Two engines run a GEMM:
     ``ext.linear_fwd`` (the 8-phase 256-tile kernel of csrc/gemm8p.hip where
     N % 256 == 0, K % 64 == 0 and K >= 128, else the 128-tile kernels of
     csrc/gemm.hip for any K % 64 == 0), with the bias / activation / residual /
-    dropout epilogues and the activation backward fused into the GEMM; dW on
+    dropout epilogues and the activation backward fused into the GEMM; where
+    none of those takes a shape that ran on rocBLAS so far (dX and fc2-dX off
+    the 8-phase grid, a forward with K % 64 != 0, the fused block at widths
+    off the 256 grid), the 128-tile NT kernel of csrc/gemm_nt128.hip for any
+    N % 8 == 0, K % 8 == 0 with M >= 256 and K <= 576 (``_nt128_ok``); dW on
     the split-M TN kernels (fp32 accumulate), which can fold the bias
     gradient out of their operands: the 256-tile kernel of csrc/gemm_tn8p.hip
     where N % 256 == 0 and K % 256 == 0, else the 128-tile kernel of
@@ -117,12 +121,59 @@ def _deterministic() -> bool:
 # ---------------------------------------------------------------------------
 
 
-def gemm_fwd(ext, x2, w, b, act, res2, *, hip: bool, save=None, drop=None):
+# Fewest rows at which a forward / dX GEMM off the 8-phase grid goes to the
+# 128-tile NT kernel (csrc/gemm_nt128.hip). At the floor itself the call is
+# two row tiles and launch-bound: (256 | 1024, 1152, 384) and (256, 384, 384)
+# measured 0.010 ms against addmm's 0.021. Below it the traces the route
+# tests pin at M = 80 and M = 8 stay as they are; not measured there.
+_NT128_MIN_M = 256
+# Longest contraction at which it does. Its K loop runs at 0.55-0.75 PF/s
+# where rocBLAS reaches 0.8-1.15, and what it saves is the separate epilogue
+# pass and rocBLAS's weaker short-K tiles: at M = 201728 / 46656 every site
+# with K <= 576 measured level or ahead (up to 1.45x) and every site with
+# K >= 768 but one behind (1.03-1.68x the time), under either staging design
+# that was built; profiles/nt_offgrid_NOTES.md.
+_NT128_MAX_K = 576
+
+
+def nt128_rows_k_ok(M: int, K: int) -> bool:
+    """The two routing conditions above, and nothing under set_fp8(True):
+    every route of that mode stays what it was."""
+    return M >= _NT128_MIN_M and K <= _NT128_MAX_K and not _FP8_STATE["enabled"]
+
+
+def _nt128_ok(ext, x2: torch.Tensor, w: torch.Tensor | None, N: int) -> bool:
+    """Whether x2 (M, K) @ w (N, K)^T may run the 128-tile NT kernel: its
+    domain (N and K multiples of 8, contiguous 16-byte-aligned bf16 operands)
+    and the routing conditions of nt128_rows_k_ok. w is None where the
+    caller is about to make the weight operand itself (the transposed copy
+    of a dX GEMM)."""
+    M, K = x2.shape
+    return (
+        nt128_rows_k_ok(M, K)
+        and x2.dtype == torch.bfloat16
+        and ext.gemm_nt_128_supported(M, N, K)
+        and x2.is_contiguous()
+        and x2.data_ptr() % 16 == 0
+        and (w is None or (w.dtype == torch.bfloat16 and w.is_contiguous()
+                           and w.data_ptr() % 16 == 0))
+    )
+
+
+def gemm_fwd(ext, x2, w, b, act, res2, *, hip: bool, save=None, drop=None, nt128: bool = False):
     """y = act(x2 @ w^T + b) [+ res2] -> (y, saved). save: None, "z" (the
     bf16 pre-activation) or "g" (the fp16 derivative act'(pre), in-house
     engine only). drop = (p, rng, site): dropout fused into the in-house
-    epilogue. hip is the caller's engine choice."""
+    epilogue. hip is the caller's engine choice; with nt128 a shape the
+    8-phase kernel does not take runs the 128-tile NT kernel (no dropout
+    form) where _nt128_ok admits it, and rocBLAS otherwise, instead of the
+    kernels behind linear_fwd."""
     act = act or ""
+    if hip and nt128 and not ext.gemm8p_supported(x2.shape[0], w.shape[0], w.shape[1]):
+        if drop is None and _nt128_ok(ext, x2, w, w.shape[0]):
+            return tuple(ext.gemm_nt_128(x2, w, b, act, res2,
+                                         {None: "none", "z": "pre", "g": "grad"}[save]))
+        hip = False
     if hip:
         drop = drop or ()
         if save == "g":
@@ -164,14 +215,14 @@ def gemm_dx(ext, dz: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     w.t().contiguous() + two quantization passes cost more than the fp8
     GEMM saves. The fused-block path instead runs fc1-dX on fp8 with a
     producer-emitted e4m3 operand — see ops/block.py.)"""
-    if (
-        _gemm_mode() == "hip"
-        and dz.dtype == torch.bfloat16
-        and ext.gemm8p_supported(dz.shape[0], w.shape[1], w.shape[0])
-    ):
-        wt = w.t().contiguous()
-        y, _ = ext.linear_fwd(dz, wt, None, "", None, False)
-        return y
+    if _gemm_mode() == "hip" and dz.dtype == torch.bfloat16:
+        if ext.gemm8p_supported(dz.shape[0], w.shape[1], w.shape[0]):
+            wt = w.t().contiguous()
+            y, _ = ext.linear_fwd(dz, wt, None, "", None, False)
+            return y
+        # off the 8-phase grid: the 128-tile NT kernel
+        if w.dtype == torch.bfloat16 and _nt128_ok(ext, dz, None, w.shape[1]):
+            return ext.gemm_nt_128(dz, w.t().contiguous())[0]
     return torch.matmul(dz, w)
 
 
@@ -179,12 +230,17 @@ def gemm_dx_act(ext, dy2, w, saved, act, *, hip: bool) -> torch.Tensor:
     """dz = (dy2 @ w) * act'(pre), the dX of an activated linear, from what
     its forward saved: the fp16 derivative (one multiply in the epilogue), or
     the bf16 pre-activation — the derivative recomputed in the epilogue where
-    the caller's engine is the in-house one (hip) and the 8-phase kernel
-    takes the shape, else rocBLAS + a separate act_bwd pass."""
+    the caller's engine is the in-house one (hip) and the 8-phase or the
+    128-tile NT kernel takes the shape, else rocBLAS + a separate act_bwd
+    pass. The 8-phase kernel goes first wherever it takes the shape."""
+    p8 = ext.gemm8p_supported(dy2.shape[0], w.shape[1], w.shape[0])
     if saved.dtype == torch.float16:
-        return ext.gemm_nt_8p_gradmul(dy2, w.t().contiguous(), saved)
-    if hip and ext.gemm8p_supported(dy2.shape[0], w.shape[1], w.shape[0]):
+        gradmul = ext.gemm_nt_8p_gradmul if p8 else ext.gemm_nt_128_gradmul
+        return gradmul(dy2, w.t().contiguous(), saved)
+    if hip and p8:
         return ext.gemm_nt_8p_gradact(dy2, w.t().contiguous(), saved, act)
+    if hip and w.dtype == torch.bfloat16 and _nt128_ok(ext, dy2, None, w.shape[1]):
+        return ext.gemm_nt_128_gradact(dy2, w.t().contiguous(), saved, act)
     return ext.act_bwd(torch.matmul(dy2, w), saved, act)
 
 
@@ -270,7 +326,14 @@ class _LinearActFn(torch.autograd.Function):
                 y = ext.bias_act_fwd(z, b, act or "", res2)
         else:
             hip = _gemm_mode() == "hip" and ext.gemm_supported(x2.shape[0], out_f, in_f, str(x2.dtype))
-            y, z = gemm_fwd(ext, x2, w, b, act, res2, hip=hip, save="z" if act is not None else None)
+            # a contraction length off the 64 grid is served by no kernel
+            # behind linear_fwd: the 128-tile NT kernel, within its K cap
+            # ((201728, 384, 328) measured 0.158 ms against addmm's 0.168;
+            # so400m's 4304 is beyond the cap and stays on rocBLAS)
+            nt128 = (not hip and _gemm_mode() == "hip" and in_f % 64 != 0
+                     and _nt128_ok(ext, x2, w, out_f))
+            y, z = gemm_fwd(ext, x2, w, b, act, res2, hip=hip or nt128, nt128=nt128,
+                            save="z" if act is not None else None)
         if act is not None:
             ctx.save_for_backward(x2, w, z)
         else:

@@ -34,6 +34,7 @@ setup(
                 "jimm_amd/csrc/gemm8p_f8.hip",
                 "jimm_amd/csrc/gemm_tn8p.hip",
                 "jimm_amd/csrc/gemm_tn128.hip",
+                "jimm_amd/csrc/gemm_nt128.hip",
                 "jimm_amd/csrc/losses.hip",
                 "jimm_amd/csrc/simloss.hip",
                 "jimm_amd/csrc/probe.hip",
