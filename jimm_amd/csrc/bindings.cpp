@@ -76,6 +76,14 @@ std::vector<torch::Tensor> gemm_nt_128(torch::Tensor x, torch::Tensor w,
 torch::Tensor gemm_nt_128_gradmul(torch::Tensor dy, torch::Tensor wt, torch::Tensor g);
 torch::Tensor gemm_nt_128_gradact(torch::Tensor dy, torch::Tensor wt, torch::Tensor z,
                                   std::string act);
+bool gemm_nt_8p_ragged_supported(int64_t M, int64_t N, int64_t K);
+std::vector<torch::Tensor> gemm_nt_8p_ragged(torch::Tensor x, torch::Tensor w,
+                                             c10::optional<torch::Tensor> bias, std::string act,
+                                             c10::optional<torch::Tensor> residual,
+                                             std::string save, double p);
+torch::Tensor gemm_nt_8p_ragged_gradmul(torch::Tensor dy, torch::Tensor wt, torch::Tensor g);
+torch::Tensor gemm_nt_8p_ragged_gradact(torch::Tensor dy, torch::Tensor wt, torch::Tensor z,
+                                        std::string act);
 torch::Tensor tr16_probe(torch::Tensor src, int64_t mode);
 std::vector<torch::Tensor> linear_fwd(torch::Tensor x, torch::Tensor w,
                                       c10::optional<torch::Tensor> bias, std::string act,
@@ -176,6 +184,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "128-tile dX GEMM times a saved fp16 activation derivative");
   m.def("gemm_nt_128_gradact", &gemm_nt_128_gradact,
         "128-tile dX GEMM with fused act-backward epilogue");
+  m.def("gemm_nt_8p_ragged_supported", &gemm_nt_8p_ragged_supported,
+        "ragged 8-phase NT GEMM shape check (N, K multiples of 8, K >= 128)");
+  m.def("gemm_nt_8p_ragged", &gemm_nt_8p_ragged,
+        "NT GEMM, 256x256 tiles on the 8-phase kernel, ragged M / N / K, fused epilogue -> "
+        "(y, z | None); save: none | pre | grad; p > 0 (dropout) is refused",
+        py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("act") = "",
+        py::arg("residual") = py::none(), py::arg("save") = "none", py::arg("p") = 0.0);
+  m.def("gemm_nt_8p_ragged_gradmul", &gemm_nt_8p_ragged_gradmul,
+        "ragged 8-phase dX GEMM times a saved fp16 activation derivative");
+  m.def("gemm_nt_8p_ragged_gradact", &gemm_nt_8p_ragged_gradact,
+        "ragged 8-phase dX GEMM with fused act-backward epilogue");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 lane-mapping probe");
   m.def("l2norm_fwd", &l2norm_fwd, "row L2-normalize forward (K12)");
   m.def("l2norm_bwd", &l2norm_bwd, "row L2-normalize backward (K12)");

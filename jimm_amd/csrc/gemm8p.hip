@@ -33,6 +33,22 @@
 // (A0 staged t.p2 first read t+1.p0; A1 t.p3 -> t+1.p1; B t.p0/p1 ->
 // t+1.p0).  The last tile's p0 drains with vmcnt(0) (its stages were the
 // newest and the stream has ended).
+// K tail (KTAIL, K % 64 = 8 .. 56 columns behind the nk whole tiles): after the
+// loop every thread loads the 16-byte chunk stage_base gives it at column
+// nk*64 if that chunk ends at or before K, zeros otherwise (nothing beyond a
+// row's end is read, nothing stale is multiplied), and writes it with one
+// ds_write_b128 at the lane-linear image offset the DMA would have used, so
+// swizzle, offA and offB hold. The images are those tile nk would have used:
+// A buffer nk & 1, last read in tile nk-2, and the next B slot of the cycle,
+// last read in tile nk-3 — both 4 or more barriers back, and no DMA is in
+// flight since the last tile's vmcnt(0). lgkmcnt(0), ONE barrier, then one
+// more tile's fragment reads and MFMAs with no staging (the kh = 0 pair alone
+// when the tail is at most 32 columns).
+// Ragged N (NGUARD): ceil(N/256) tile columns; a W staging row beyond N reads
+// row N-1 (clamped after the permutation), and what it brings in lands only in
+// accumulator columns the epilogue never stores. Waves whose 64 columns lie
+// wholly beyond N skip their fragment reads and MFMAs, wave-uniformly; they
+// stage, wait and arrive at every barrier like the others.
 //
 // LDS image swizzle: byte(row, c16) = row*128 + (c16 ^ (row&7))*16 —
 // verified conflict-free for this read pattern (SQ_LDS_BANK_CONFLICT = 0,
@@ -69,7 +85,10 @@
 // into the two forward forms the MLP has: a lane's 16 elements of a fragment
 // are the 4 words x 2 halves of two Philox calls, made in the epilogue loops.
 // M may be ragged (MGUARD clamps staging rows and predicates stores);
-// N%256==0, K%64==0, K>=128 required (gemm8p_supported). The 8-byte accesses
+// N%256==0, K%64==0, K>=128 required (gemm8p_supported); the ragged form
+// (gemm_nt_8p_ragged*: NGUARD + KTAIL, no dropout or e4m3 form) takes any
+// N%8==0, K%8==0, K>=128, which keeps every row 16-byte aligned for the glds
+// and every 4-column group 8-byte aligned. The 8-byte accesses
 // need 8-byte aligned y / residual / z / g and bf16 bias, a 16-byte aligned
 // fp32 bias and a 4-byte aligned e4m3 output; N%256==0 keeps every row and
 // column offset aligned, the base pointers are checked in launch_8p.
@@ -77,6 +96,8 @@
 #include <torch/extension.h>
 #include <hip/hip_fp8.h>
 #include <ATen/hip/HIPContext.h>
+
+#include <climits>
 
 #include "mfma.h"
 
@@ -119,18 +140,25 @@ __device__ __forceinline__ int frag_off(int row, int chunk) {
   return (row << 7) + ((chunk ^ (row & 7)) << 4);
 }
 
+// NGUARD: N may be ragged (any N % 8 == 0). KTAIL: K may be (any K % 8 == 0,
+// K >= 128). Both off: the grid kernel. Both on (with MGUARD): the ragged
+// kernel, whose epilogue keeps its fp32 arithmetic out of packed pairs
+// (gemm_epilogue4's NOPK, mfma.h).
 template <int ACT, bool HAS_BIAS, bool HAS_RES, int SAVE, bool MGUARD, int GRADM = GRADM_NONE,
-          bool FP8O = false, bool DROP = false>
+          bool FP8O = false, bool DROP = false, bool NGUARD = false, bool KTAIL = false>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
     const bf16* __restrict__ X, const bf16* __restrict__ W, const void* __restrict__ bias,
     int bias_bf16, const bf16* __restrict__ res, bf16* __restrict__ Y, bf16* __restrict__ Z,
     int M, int N, int K, unsigned char* __restrict__ Y8 = nullptr,
     const float* __restrict__ scale8 = nullptr,
     unsigned int* __restrict__ amax_bits = nullptr, drop_args drop = {}) {
+  static_assert(!(NGUARD || KTAIL) || (!DROP && !FP8O), "no ragged dropout or e4m3 form");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // A images: [buf 0..1][half 0..1] at (buf*2+half)*16 KiB;
   // B images: [slot 0..2][half 0..1] at 64 KiB + (slot*2+half)*16 KiB.
-  auto As = [&](int buf, int h) { return smem + (buf * 2 + h) * HALF_BYTES; };
+  auto As = [&](int buf, int h) {
+    return smem + (buf * 2 + h) * HALF_BYTES;
+  };
   auto Bs = [&](int slot, int h) {
     return smem + 4 * HALF_BYTES + (slot * 2 + h) * HALF_BYTES;
   };
@@ -144,12 +172,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
   const int lo = lane & 15, hi = lane >> 4;
 
   const int mt = MGUARD ? (M + BM - 1) / BM : M / BM;
-  const int nt = N / BN;
+  const int nt = NGUARD ? (N + BN - 1) / BN : N / BN;
   const int wg = xcd_remap(blockIdx.x, mt * nt);
   const int m0 = (wg / nt) * BM;
   const int n0 = (wg % nt) * BN;
   const int wm = (wave >> 2);  // 0..1
   const int wn = (wave & 3);   // 0..3
+  // NGUARD: a wave whose 64 columns lie wholly beyond N has nothing to store;
+  // it skips its fragment reads and MFMAs (wave-uniform) and still stages and
+  // arrives at every barrier
+  const bool active = !NGUARD || n0 + __builtin_amdgcn_readfirstlane(wn) * 64 < N;
 
   f32x4_t acc[2][4][4] = {};  // [pr][mi][ni]
 
@@ -162,7 +194,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       asrc[h][r] = stage_base<MGUARD>(X, K, m0 + h * 128, M, r, tid);
-      bsrc[h][r] = stage_base<false, PERM>(W + (int64_t)n0 * K, K, h * 128, N, r, tid);
+      // NGUARD: the absolute W row, clamped to N - 1 AFTER the permutation
+      // (what a clamped row brings in lands in columns that are never stored)
+      if constexpr (NGUARD) bsrc[h][r] = stage_base<true, PERM>(W, K, n0 + h * 128, N, r, tid);
+      else bsrc[h][r] = stage_base<false, PERM>(W + (int64_t)n0 * K, K, h * 128, N, r, tid);
     }
   const int ldst = tid * 16;  // lds dest byte of round 0
   auto stageA = [&](int kt, int h) {
@@ -210,10 +245,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
     for (int kh = 0; kh < 2; ++kh) {
       // ---- pr = 0 phase: read A0-frags + B-frags(kh), stage, MFMA ----
       bf16x8_t xa[4], wb[4];
+      if (active) {
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi) xa[mi] = lds_frag8p(a0i, offA[kh][mi]);
+        for (int mi = 0; mi < 4; ++mi) xa[mi] = lds_frag8p(a0i, offA[kh][mi]);
 #pragma unroll
-      for (int ni = 0; ni < 4; ++ni) wb[ni] = lds_frag8p(bi, offB[kh][ni]);
+        for (int ni = 0; ni < 4; ++ni) wb[ni] = lds_frag8p(bi, offB[kh][ni]);
+      }
       if (more) {
         if (kh == 0) stageB(t + 1, slot1, 0);
         else stageA(t + 1, 0);
@@ -226,16 +263,20 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
       }
       raw_barrier();
       __builtin_amdgcn_s_setprio(1);
+      if (active) {
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
+        for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          acc[0][mi][ni] = MFMA16(xa[mi], wb[ni], acc[0][mi][ni]);
+          for (int ni = 0; ni < 4; ++ni)
+            acc[0][mi][ni] = MFMA16(xa[mi], wb[ni], acc[0][mi][ni]);
+      }
       __builtin_amdgcn_s_setprio(0);
 
       // ---- pr = 1 phase: read A1-frags, REUSE B-frags, stage, MFMA ----
+      if (active) {
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi) xa[mi] = lds_frag8p(a1i, offA[kh][mi]);
+        for (int mi = 0; mi < 4; ++mi) xa[mi] = lds_frag8p(a1i, offA[kh][mi]);
+      }
       if (more) {
         if (kh == 0) stageB(t + 1, slot1, 1);
         else stageA(t + 1, 1);
@@ -244,19 +285,84 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
       else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
       raw_barrier();
       __builtin_amdgcn_s_setprio(1);
+      if (active) {
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
+        for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          acc[1][mi][ni] = MFMA16(xa[mi], wb[ni], acc[1][mi][ni]);
+          for (int ni = 0; ni < 4; ++ni)
+            acc[1][mi][ni] = MFMA16(xa[mi], wb[ni], acc[1][mi][ni]);
+      }
       __builtin_amdgcn_s_setprio(0);
     }
     slot = slot1;
     slot1 = slot1 + 1 == 3 ? 0 : slot1 + 1;
   }
 
+  if constexpr (KTAIL) {
+    // K tail (file header): the K % 64 columns behind the nk whole tiles,
+    // through registers with zero fill into the images tile nk would have
+    // used, one barrier, one more walk without staging.
+    const int ktail = K - nk * BK;  // 0, 8 .. 56
+    if (ktail) {
+      // this thread's chunk of a staged row, the same in both rounds
+      // (stage_base: row & 7 == (tid >> 3) & 7 in either)
+      const bool in_k = (((tid & 7) ^ ((tid >> 3) & 7)) << 3) < ktail;
+      bf16x8_t ta[2][2], tb[2][2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          ta[h][r] = tb[h][r] = bf16x8_t{};
+          if (in_k) {  // the chunk ends at or before K: nothing beyond a row's end is read
+            ta[h][r] = *reinterpret_cast<const bf16x8_t*>(asrc[h][r] + (int64_t)nk * BK);
+            tb[h][r] = *reinterpret_cast<const bf16x8_t*>(bsrc[h][r] + (int64_t)nk * BK);
+          }
+        }
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          *reinterpret_cast<bf16x8_t*>(As(nk & 1, h) + r * 8192 + ldst) = ta[h][r];
+          *reinterpret_cast<bf16x8_t*>(Bs(slot, h) + r * 8192 + ldst) = tb[h][r];
+        }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      raw_barrier();
+      if (active) {
+        const char* a0i = As(nk & 1, 0);
+        const char* a1i = As(nk & 1, 1);
+        const char* bi = Bs(slot, bh);
+#pragma unroll
+        for (int kh = 0; kh < 2; ++kh) {
+          if (kh == 1 && ktail <= 32) break;  // the second K-half is all zeros
+          bf16x8_t xa[4], wb[4];
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi) xa[mi] = lds_frag8p(a0i, offA[kh][mi]);
+#pragma unroll
+          for (int ni = 0; ni < 4; ++ni) wb[ni] = lds_frag8p(bi, offB[kh][ni]);
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+              acc[0][mi][ni] = MFMA16(xa[mi], wb[ni], acc[0][mi][ni]);
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi) xa[mi] = lds_frag8p(a1i, offA[kh][mi]);
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+              acc[1][mi][ni] = MFMA16(xa[mi], wb[ni], acc[1][mi][ni]);
+        }
+      }
+    }
+  }
+
   // Epilogue: acc[pr][mi][ni] -> rows m0 + pr*128 + wm*64 + 16mi + hi*4 + r,
   // cols n0 + wn*64 + 4lo + ni (PERM) or n0 + wn*64 + 16ni + lo (DROP).
+  // NGUARD: a lane's 4 columns lie wholly inside or wholly beyond N (N % 8 ==
+  // 0), so one predicate covers its bias load and every store.
+  if constexpr (NGUARD) {
+    if (n0 + wn * 64 + 4 * lo >= N) return;
+  }
   float rs8 = 1.f, tmax = 0.f;
   if (FP8O) rs8 = fast_rcpf(scale8[0]);
   // a lane owns 4 columns (n depends on ni alone): its bias values, once
@@ -315,8 +421,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
           if (MGUARD && m >= M) continue;
           const float v4[4] = {acc[pr][mi][0][r], acc[pr][mi][1][r], acc[pr][mi][2][r],
                                acc[pr][mi][3][r]};
-          gemm_epilogue4<ACT, HAS_BIAS, HAS_RES, SAVE, GRADM, FP8O>(v4, m, n, N, bv, res, Y, Z,
-                                                                    Y8, rs8, &tmax);
+          gemm_epilogue4<ACT, HAS_BIAS, HAS_RES, SAVE, GRADM, FP8O, NGUARD || KTAIL>(
+              v4, m, n, N, bv, res, Y, Z, Y8, rs8, &tmax);
         }
       }
     }
@@ -327,10 +433,22 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_8p_kernel(
   }
 }
 
+// The ragged kernel: MGUARD, NGUARD and KTAIL all on (a shape without a K tail
+// skips that step at run time).
+template <int ACT, bool HAS_BIAS, bool HAS_RES, int SAVE, int GRADM = GRADM_NONE>
+constexpr auto gemm_nt_8p_ragged_kernel =
+    gemm_nt_8p_kernel<ACT, HAS_BIAS, HAS_RES, SAVE, true, GRADM, false, false, true, true>;
+
 }  // namespace
 
 bool gemm8p_supported(int64_t M, int64_t N, int64_t K) {
   return M >= 1 && (N % BN == 0) && (K % BK == 0) && K >= 2 * BK;
+}
+
+bool gemm_nt_8p_ragged_supported(int64_t M, int64_t N, int64_t K) {
+  return M >= 1 && N >= 8 && N % 8 == 0 && K % 8 == 0 && K >= 2 * BK && M <= INT_MAX - BM &&
+         N <= INT_MAX - BN && K <= INT_MAX &&
+         ((M + BM - 1) / BM) * ((N + BN - 1) / BN) <= INT_MAX;
 }
 
 namespace {
@@ -355,8 +473,8 @@ void launch_8p(const torch::Tensor& x, const torch::Tensor& w, const void* biasp
                 "8-phase GEMM: a bf16 bias must be 8-byte, an fp32 bias 16-byte aligned");
   }
   constexpr size_t shmem = 10 * HALF_BYTES;
-  const int mt = (M + BM - 1) / BM;
-  launch_lds<Kernel>(dim3(mt * (N / BN)), dim3(NTHREADS), shmem, shmem,
+  const int mt = (M + BM - 1) / BM, nt = (N + BN - 1) / BN;  // (ragged N: the ragged kernel)
+  launch_lds<Kernel>(dim3(mt * nt), dim3(NTHREADS), shmem, shmem,
                      at::hip::getCurrentHIPStream(), reinterpret_cast<const bf16*>(x.data_ptr()),
                      reinterpret_cast<const bf16*>(w.data_ptr()), biasp, bias_bf16, resp,
                      reinterpret_cast<bf16*>(y.data_ptr()), zp, M, N, K, y8p, scale8p, amaxp,
@@ -482,4 +600,112 @@ void gemm_nt_8p(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> b
           bias.has_value(), residual.has_value(), (M % BM) != 0);
     });
   });
+}
+
+// ---- the ragged kernel's entry points (the gemm_nt_128 set, gemm_nt128.hip) --
+
+namespace {
+
+// Checks shared by the three entry points, all ahead of any launch: x (M, K)
+// and w (N, K) contiguous 16-byte-aligned bf16 inside the kernel's domain.
+void check_8pr(const char* op, const torch::Tensor& x, const torch::Tensor& w) {
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 2 && w.dim() == 2, op,
+              ": x (M, K) and w (N, K) must be 2-d CUDA tensors");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16, op,
+              ": operands must be bf16");
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), op, ": operands must be contiguous");
+  TORCH_CHECK(w.size(1) == x.size(1) &&
+                  gemm_nt_8p_ragged_supported(x.size(0), w.size(0), x.size(1)),
+              op, ": needs M >= 1, N and K multiples of 8 and K >= 128, got x ", x.sizes(), " w ",
+              w.sizes());
+  auto aligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  TORCH_CHECK(aligned(x.data_ptr()) && aligned(w.data_ptr()), op,
+              ": operands must be 16-byte aligned");
+}
+
+}  // namespace
+
+// y = act(x @ w^T + bias) [+ residual] -> {y, z}: z per `save` — "none"
+// (undefined = None in Python), "pre" (the bf16 pre-activation) or "grad" (the
+// fp16 activation derivative; needs an activation). bias: fp32 or bf16, read
+// as it is; any other dtype goes through fp32. p: a dropout probability; the
+// ragged kernel has no dropout form and refuses p > 0.
+std::vector<torch::Tensor> gemm_nt_8p_ragged(torch::Tensor x, torch::Tensor w,
+                                             c10::optional<torch::Tensor> bias, std::string act,
+                                             c10::optional<torch::Tensor> residual,
+                                             std::string save, double p) {
+  check_8pr("gemm_nt_8p_ragged", x, w);
+  TORCH_CHECK(p == 0.0, "gemm_nt_8p_ragged: no dropout form (p = ", p, ")");
+  const int64_t M = x.size(0), N = w.size(0);
+  const int save_c =
+      save == "none" ? SAVE_NONE : save == "pre" ? SAVE_PRE : save == "grad" ? SAVE_GRAD : -1;
+  TORCH_CHECK(save_c >= 0, "gemm_nt_8p_ragged: save must be none, pre or grad, got ", save);
+  const int act_i = act_code(act);
+  TORCH_CHECK(save_c != SAVE_GRAD || act_i != ACT_NONE,
+              "saving the activation derivative needs an activation");
+  if (residual)
+    TORCH_CHECK(residual->is_cuda() && residual->is_contiguous() &&
+                    residual->scalar_type() == torch::kBFloat16 && residual->numel() == M * N,
+                "gemm_nt_8p_ragged: the residual must be a contiguous bf16 (M, N)");
+  c10::optional<torch::Tensor> b;
+  if (bias) {
+    TORCH_CHECK(bias->is_cuda() && bias->numel() == N,
+                "gemm_nt_8p_ragged: bias must hold N values");
+    b = bias->contiguous();
+    if (b->scalar_type() != torch::kBFloat16 && b->scalar_type() != torch::kFloat32)
+      b = b->to(torch::kFloat32);
+  }
+  auto y = torch::empty({M, N}, x.options());
+  torch::Tensor z;
+  if (save_c == SAVE_PRE) z = torch::empty({M, N}, x.options());
+  if (save_c == SAVE_GRAD) z = torch::empty({M, N}, x.options().dtype(torch::kFloat16));
+  const void* biasp = b ? b->data_ptr() : nullptr;
+  const int bias_bf16 = b && b->scalar_type() == torch::kBFloat16;
+  const bf16* resp = residual ? reinterpret_cast<const bf16*>(residual->data_ptr()) : nullptr;
+  bf16* zp = z.defined() ? reinterpret_cast<bf16*>(z.data_ptr()) : nullptr;
+  with_act(act_i, [&](auto act_c) {
+    with_save(save_c, [&](auto sv) {
+      with_flags(
+          [&](auto hb, auto hr) {
+            constexpr int A = decltype(act_c)::value, S = decltype(sv)::value;
+            if constexpr (S != SAVE_GRAD || A != ACT_NONE)
+              launch_8p<gemm_nt_8p_ragged_kernel<A, decltype(hb)::value, decltype(hr)::value, S>>(
+                  x, w, biasp, bias_bf16, resp, y, zp);
+          },
+          bias.has_value(), residual.has_value());
+    });
+  });
+  return {y, z};
+}
+
+// dz = (dy @ wt^T) * g on a pre-transposed wt (in_f, out_f), g the fp16
+// activation derivative a SAVE_GRAD forward stored.
+torch::Tensor gemm_nt_8p_ragged_gradmul(torch::Tensor dy, torch::Tensor wt, torch::Tensor g) {
+  check_8pr("gemm_nt_8p_ragged_gradmul", dy, wt);
+  TORCH_CHECK(g.is_cuda() && g.is_contiguous() && g.scalar_type() == torch::kFloat16 &&
+                  g.dim() == 2 && g.size(0) == dy.size(0) && g.size(1) == wt.size(0),
+              "gemm_nt_8p_ragged_gradmul: g must be a contiguous fp16 (M, N)");
+  auto y = torch::empty({dy.size(0), wt.size(0)}, dy.options());
+  launch_8p<gemm_nt_8p_ragged_kernel<ACT_NONE, false, true, SAVE_NONE, GRADM_MUL>>(
+      dy, wt, nullptr, 0, reinterpret_cast<const bf16*>(g.data_ptr()), y, nullptr);
+  return y;
+}
+
+// dz = (dy @ wt^T) * act'(z), z the saved bf16 pre-activation.
+torch::Tensor gemm_nt_8p_ragged_gradact(torch::Tensor dy, torch::Tensor wt, torch::Tensor z,
+                                        std::string act) {
+  check_8pr("gemm_nt_8p_ragged_gradact", dy, wt);
+  TORCH_CHECK(z.is_cuda() && z.is_contiguous() && z.scalar_type() == torch::kBFloat16 &&
+                  z.dim() == 2 && z.size(0) == dy.size(0) && z.size(1) == wt.size(0),
+              "gemm_nt_8p_ragged_gradact: z must be a contiguous bf16 (M, N)");
+  const int act_i = act_code(act);
+  TORCH_CHECK(act_i != ACT_NONE, "gradact needs an activation, got ", act);
+  auto y = torch::empty({dy.size(0), wt.size(0)}, dy.options());
+  with_act(act_i, [&](auto act_c) {
+    constexpr int A = decltype(act_c)::value;
+    if constexpr (A != ACT_NONE)
+      launch_8p<gemm_nt_8p_ragged_kernel<A, false, true, SAVE_NONE, GRADM_ACT>>(
+          dy, wt, nullptr, 0, reinterpret_cast<const bf16*>(z.data_ptr()), y, nullptr);
+  });
+  return y;
 }

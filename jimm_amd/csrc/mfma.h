@@ -279,8 +279,10 @@ __device__ __forceinline__ void after(float& x, unsigned int tok) {
 // gemm_epilogue in some; those results agree to rounding, not bit for bit.
 // Without an activation there is nothing to contract (adds, or one multiply)
 // and the packing is left alone.
+// NOPK chains the elements in every form, so that no fp32 arithmetic of the
+// call is packed in pairs at all (the ragged 8-phase kernel).
 template <int ACT, bool HAS_BIAS, bool HAS_RES, int SAVE, int GRADM = GRADM_NONE,
-          bool FP8O = false>
+          bool FP8O = false, bool NOPK = false>
 __device__ __forceinline__ void gemm_epilogue4(const float (&acc4)[4], int m, int n, int N,
                                                const float (&bias4)[4], const bf16* res, bf16* Y,
                                                bf16* Z, unsigned char* Y8 = nullptr,
@@ -288,7 +290,7 @@ __device__ __forceinline__ void gemm_epilogue4(const float (&acc4)[4], int m, in
   static_assert(SAVE != SAVE_GRAD || ACT != ACT_NONE, "SAVE_GRAD needs an activation");
   typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
   constexpr bool READS = GRADM != GRADM_NONE || HAS_RES;  // res holds a residual, z or g
-  constexpr bool CHAIN = ACT != ACT_NONE;
+  constexpr bool CHAIN = ACT != ACT_NONE || NOPK;
   const int64_t at = (int64_t)m * N + n;
   float vpre[4], vy[4], in4[4] = {};
   u16x4 g4 = {};

@@ -30,6 +30,7 @@ from jimm_amd.ops.functional import _split_heads
 from jimm_amd.ops.hip_linear import (
     _FP8_STATE,
     _nt128_ok,
+    _nt8pr_ok,
     _gemm_mode,
     _quant_e4m3,
     fp8_hip,
@@ -39,6 +40,7 @@ from jimm_amd.ops.hip_linear import (
     gemm_fwd,
     gemm_fwd_f8,
     nt128_rows_k_ok,
+    nt8pr_rows_ok,
 )
 from jimm_amd.ops.philox_dropout import dropout_threshold
 
@@ -50,7 +52,7 @@ def _grid_widths(H: int, mlp_dim: int) -> bool:
 
 def _hip_gemms(H: int, mlp_dim: int, M: int = 0, fp8: bool = False) -> bool:
     """True when the encoder block's forward GEMMs run on the in-house MFMA
-    kernels (JIMM_AMD_GEMM=hip, the default). Two arms:
+    kernels (JIMM_AMD_GEMM=hip, the default). Three arms:
       * H % 256 == 0 puts qkv, proj and fc2 (N = 3H, H, H) on the 8-phase
         kernel, and every K (H or mlp_dim) must be a multiple of 64 for any
         of them. fc1 (N = mlp_dim) takes the 128-tile kernels of gemm.hip
@@ -62,7 +64,15 @@ def _hip_gemms(H: int, mlp_dim: int, M: int = 0, fp8: bool = False) -> bool:
         proj; not fc2, whose K = mlp_dim is beyond the cap) and rocBLAS
         otherwise. so400m (H = 1152) is beyond the cap. Not with the
         block's fp8 state on (fp8): its backward arm hands fc2-dX to the
-        8-phase e4m3-emitting kernel, which takes no off-grid shape.
+        8-phase e4m3-emitting kernel, which takes no off-grid shape;
+      * widths that are multiples of 8 with M at or above the row floor of
+        the ragged 8-phase kernel and the fp8 state off (so400m 1152 / 4304
+        at M >= 32768): each GEMM asks the 8-phase kernel, the 128-tile NT
+        kernel and the ragged 8-phase kernel (_nt8pr_ok) in that order and
+        runs rocBLAS otherwise. Of so400m's sites the measured rule admits
+        fc1 and fc2-dX (N = 4304), so fc1 saves the fp16 derivative and
+        fc2-dX is one gradmul GEMM; the block measured 10.56 ms against
+        10.70 (profiles/nt_ragged_NOTES.md).
         Deliberately not routed: at K = 384 (ViT-S qkv and proj forward) the
         two-buffer kernel behind linear_fwd measured 16-24% ahead of
         gemm_nt128.hip, which in turn is 1.4-2x ahead of it at K = 192 and
@@ -72,7 +82,8 @@ def _hip_gemms(H: int, mlp_dim: int, M: int = 0, fp8: bool = False) -> bool:
     if _gemm_mode() != "hip":
         return False
     return _grid_widths(H, mlp_dim) or (
-        not fp8 and H % 8 == 0 and mlp_dim % 8 == 0 and nt128_rows_k_ok(M, H)
+        not fp8 and H % 8 == 0 and mlp_dim % 8 == 0
+        and (nt128_rows_k_ok(M, H) or nt8pr_rows_ok(M))
     )
 
 
@@ -244,7 +255,8 @@ class EncoderBlockFn(torch.autograd.Function):
             # reads z1)
             save_g = hip and _act_save_g() and (
                 ext.gemm8p_supported(B * L, w1.shape[0], H)
-                or (nt128 and _nt128_ok(ext, h2.view(-1, H), w1, w1.shape[0])))
+                or (nt128 and (_nt128_ok(ext, h2.view(-1, H), w1, w1.shape[0])
+                               or _nt8pr_ok(ext, h2.view(-1, H), w1, w1.shape[0]))))
             if drop and not save_g:
                 raise RuntimeError("fused block: dropout needs the saved-derivative fc1 path")
             # with dropout f = act(z)*m*s and z1 = act'(z)*m*s: the mask of

@@ -10,7 +10,13 @@ Two engines run a GEMM:
     none of those takes a shape that ran on rocBLAS so far (dX and fc2-dX off
     the 8-phase grid, a forward with K % 64 != 0, the fused block at widths
     off the 256 grid), the 128-tile NT kernel of csrc/gemm_nt128.hip for any
-    N % 8 == 0, K % 8 == 0 with M >= 256 and K <= 576 (``_nt128_ok``); dW on
+    N % 8 == 0, K % 8 == 0 with M >= 256 and K <= 576 (``_nt128_ok``); what
+    that leaves, the ragged form of the 8-phase kernel (gemm_nt_8p_ragged:
+    any N % 8 == 0, K % 8 == 0, K >= 128) with M >= 32768 and N filling at
+    least 98% of its 256-wide tile columns (``_nt8pr_ok``: so400m's fc1 and
+    fc2-dX, 8% ahead of rocBLAS + its epilogue pass as a pair at M = 46656;
+    every other so400m site measured level or behind and stays on rocBLAS,
+    profiles/nt_ragged_NOTES.md); dW on
     the split-M TN kernels (fp32 accumulate), which can fold the bias
     gradient out of their operands: the 256-tile kernel of csrc/gemm_tn8p.hip
     where N % 256 == 0 and K % 256 == 0, else the 128-tile kernel of
@@ -160,19 +166,63 @@ def _nt128_ok(ext, x2: torch.Tensor, w: torch.Tensor | None, N: int) -> bool:
     )
 
 
+# Fewest rows at which a forward / dX GEMM that neither the 8-phase grid kernel
+# nor the 128-tile NT kernel takes goes to the ragged 8-phase kernel
+# (gemm_nt_8p_ragged, csrc/gemm8p.hip). The fc1 ladder of
+# profiles/nt_ragged_NOTES.md is behind rocBLAS up to 8192 rows and the routed
+# pair (below) level at 16384 and ahead from 32768.
+_NT8PR_MIN_M = 32768
+# Least share of its ceil(N / 256) tile columns that N must fill. The partial
+# last n-tile costs a whole tile's time: at N = 1152 (5 tile columns for 4.5
+# tiles of work, 90%) and 3456 (96%) the kernel measured level with or behind
+# rocBLAS at one or more of M = 16384 / 46656 / 65536, at N = 4304 (98.9%:
+# so400m's fc1 and, with the saved derivative, fc2-dX) ahead as a pair at
+# 46656 and 65536; same notes.
+_NT8PR_MIN_FILL = 0.98
+
+
+def nt8pr_rows_ok(M: int) -> bool:
+    """The row floor, and nothing under set_fp8(True)."""
+    return M >= _NT8PR_MIN_M and not _FP8_STATE["enabled"]
+
+
+def _nt8pr_ok(ext, x2: torch.Tensor, w: torch.Tensor | None, N: int) -> bool:
+    """Whether x2 (M, K) @ w (N, K)^T may run the ragged 8-phase kernel: its
+    domain (N and K multiples of 8, K >= 128, contiguous 16-byte-aligned bf16
+    operands) and the measured rule above (row floor, n-tile fill). w is None where the caller is about
+    to make the weight operand itself (the transposed copy of a dX GEMM).
+    Callers ask the 8-phase grid kernel and the 128-tile kernel first."""
+    M, K = x2.shape
+    return (
+        nt8pr_rows_ok(M)
+        and N >= _NT8PR_MIN_FILL * 256 * -(-N // 256)
+        and x2.dtype == torch.bfloat16
+        and ext.gemm_nt_8p_ragged_supported(M, N, K)
+        and x2.is_contiguous()
+        and x2.data_ptr() % 16 == 0
+        and (w is None or (w.dtype == torch.bfloat16 and w.is_contiguous()
+                           and w.data_ptr() % 16 == 0))
+    )
+
+
+_SAVE_NAMES = {None: "none", "z": "pre", "g": "grad"}
+
+
 def gemm_fwd(ext, x2, w, b, act, res2, *, hip: bool, save=None, drop=None, nt128: bool = False):
     """y = act(x2 @ w^T + b) [+ res2] -> (y, saved). save: None, "z" (the
     bf16 pre-activation) or "g" (the fp16 derivative act'(pre), in-house
     engine only). drop = (p, rng, site): dropout fused into the in-house
     epilogue. hip is the caller's engine choice; with nt128 a shape the
     8-phase kernel does not take runs the 128-tile NT kernel (no dropout
-    form) where _nt128_ok admits it, and rocBLAS otherwise, instead of the
+    form) where _nt128_ok admits it, then the ragged 8-phase kernel (none
+    either) where _nt8pr_ok does, and rocBLAS otherwise, instead of the
     kernels behind linear_fwd."""
     act = act or ""
     if hip and nt128 and not ext.gemm8p_supported(x2.shape[0], w.shape[0], w.shape[1]):
         if drop is None and _nt128_ok(ext, x2, w, w.shape[0]):
-            return tuple(ext.gemm_nt_128(x2, w, b, act, res2,
-                                         {None: "none", "z": "pre", "g": "grad"}[save]))
+            return tuple(ext.gemm_nt_128(x2, w, b, act, res2, _SAVE_NAMES[save]))
+        if drop is None and _nt8pr_ok(ext, x2, w, w.shape[0]):
+            return tuple(ext.gemm_nt_8p_ragged(x2, w, b, act, res2, _SAVE_NAMES[save]))
         hip = False
     if hip:
         drop = drop or ()
@@ -223,6 +273,9 @@ def gemm_dx(ext, dz: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
         # off the 8-phase grid: the 128-tile NT kernel
         if w.dtype == torch.bfloat16 and _nt128_ok(ext, dz, None, w.shape[1]):
             return ext.gemm_nt_128(dz, w.t().contiguous())[0]
+        # neither: the ragged 8-phase kernel, where its measured rule admits
+        if w.dtype == torch.bfloat16 and _nt8pr_ok(ext, dz, None, w.shape[1]):
+            return ext.gemm_nt_8p_ragged(dz, w.t().contiguous())[0]
     return torch.matmul(dz, w)
 
 
@@ -230,17 +283,25 @@ def gemm_dx_act(ext, dy2, w, saved, act, *, hip: bool) -> torch.Tensor:
     """dz = (dy2 @ w) * act'(pre), the dX of an activated linear, from what
     its forward saved: the fp16 derivative (one multiply in the epilogue), or
     the bf16 pre-activation — the derivative recomputed in the epilogue where
-    the caller's engine is the in-house one (hip) and the 8-phase or the
-    128-tile NT kernel takes the shape, else rocBLAS + a separate act_bwd
-    pass. The 8-phase kernel goes first wherever it takes the shape."""
+    the caller's engine is the in-house one (hip) and the 8-phase, the
+    128-tile NT or the ragged 8-phase kernel takes the shape (asked in that
+    order), else rocBLAS + a separate act_bwd pass."""
     p8 = ext.gemm8p_supported(dy2.shape[0], w.shape[1], w.shape[0])
+    nt128 = not p8 and w.dtype == torch.bfloat16 and _nt128_ok(ext, dy2, None, w.shape[1])
+    nt8pr = (not p8 and not nt128 and w.dtype == torch.bfloat16
+             and _nt8pr_ok(ext, dy2, None, w.shape[1]))
     if saved.dtype == torch.float16:
-        gradmul = ext.gemm_nt_8p_gradmul if p8 else ext.gemm_nt_128_gradmul
+        # the forward saved the derivative because one of the three takes
+        # this shape (the same (M, N, K) as fc1 itself)
+        gradmul = (ext.gemm_nt_8p_gradmul if p8 else
+                   ext.gemm_nt_8p_ragged_gradmul if nt8pr else ext.gemm_nt_128_gradmul)
         return gradmul(dy2, w.t().contiguous(), saved)
     if hip and p8:
         return ext.gemm_nt_8p_gradact(dy2, w.t().contiguous(), saved, act)
-    if hip and w.dtype == torch.bfloat16 and _nt128_ok(ext, dy2, None, w.shape[1]):
+    if hip and nt128:
         return ext.gemm_nt_128_gradact(dy2, w.t().contiguous(), saved, act)
+    if hip and nt8pr:
+        return ext.gemm_nt_8p_ragged_gradact(dy2, w.t().contiguous(), saved, act)
     return ext.act_bwd(torch.matmul(dy2, w), saved, act)
 
 
@@ -332,8 +393,19 @@ class _LinearActFn(torch.autograd.Function):
             # so400m's 4304 is beyond the cap and stays on rocBLAS)
             nt128 = (not hip and _gemm_mode() == "hip" and in_f % 64 != 0
                      and _nt128_ok(ext, x2, w, out_f))
-            y, z = gemm_fwd(ext, x2, w, b, act, res2, hip=hip or nt128, nt128=nt128,
-                            save="z" if act is not None else None)
+            # the ragged 8-phase kernel takes what is left of that (K beyond
+            # the cap: so400m's 4304) and the N % 256 != 0 shapes that
+            # linear_fwd runs on the 128-tile kernels of gemm.hip, at or above
+            # its row floor (profiles/nt_ragged_NOTES.md)
+            nt8pr = (_gemm_mode() == "hip" and not nt128
+                     and not ext.gemm8p_supported(x2.shape[0], out_f, in_f)
+                     and _nt8pr_ok(ext, x2, w, out_f))
+            if nt8pr:
+                y, z = ext.gemm_nt_8p_ragged(x2, w, b, act or "", res2,
+                                             "pre" if act is not None else "none")
+            else:
+                y, z = gemm_fwd(ext, x2, w, b, act, res2, hip=hip or nt128, nt128=nt128,
+                                save="z" if act is not None else None)
         if act is not None:
             ctx.save_for_backward(x2, w, z)
         else:
