@@ -21,6 +21,15 @@
 // attn_fwd_resident_kernel (81 <= Lq == Lk <= 256, non-causal, ViT-B L=197);
 // both D = 64, see their header comments and the dispatch in attn_fwd.
 //
+// Attention-probability dropout (template flag DROP of the tiled and the
+// resident kernel; the mask definition and the lane-sharing of its Philox
+// calls are in common.h, attn_drop_u): O = ((P o m) * s) V with P normalised
+// over ALL keys. A dropped element is a zeroed bf16 P entry in front of the PV
+// MFMA; the row max, the row sum, the rescale and lse see the undropped
+// values, and s rides on the 1/l factor of the epilogue. The small-L kernel
+// and the causal instantiations have no dropout form: with t8 > 0 the host
+// sends L <= 80 to the tiled kernel and refuses causal.
+//
 // MFMA: v_mfma_f32_16x16x32_bf16. Fragment layouts (verified on hardware by
 // csrc/probe.hip + tests/test_kernels_gpu.py::test_mfma_probe):
 //   A[i][k]: lane l holds A[l&15][(l>>4)*8 + j], j=0..7
@@ -48,11 +57,12 @@ constexpr int KVBLK = 64;   // keys per LDS tile
 // ds_write_b128 from the row-major staging registers and read as PV
 // B-fragments with tr_frags at per-lane address base + lane*8 B.
 
-template <bool CAUSAL, int DP>
+template <bool CAUSAL, int DP, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     bf16* __restrict__ o, float* __restrict__ lse, int Lq, int Lk, float scale, int H, int Dr,
-    hstride q_s, hstride k_s, hstride v_s, hstride o_s) {
+    hstride q_s, hstride k_s, hstride v_s, hstride o_s, drop_args drop = {}) {
+  static_assert(!(DROP && CAUSAL), "no causal dropout form");
   // Strides are those of the (B,H,L,D) views; the innermost dim is
   // contiguous. Covers contiguous BHLD, (B,L,H,D) and fused-qkv (B,L,3,H,D)
   // layouts with no permute copies.
@@ -105,6 +115,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
   }
 
   short* my_p = p_lds + wave * 16 * LDS_PITCH;
+  drop_key dkey = {};
+  if constexpr (DROP) dkey = load_drop_key(drop);
 
   f32x4 acc_o[NSTRIP][NT] = {};  // O tiles: rows q = hi*4+r, cols d = 16*dt+lo
   float m_run[NSTRIP], l_run[NSTRIP];
@@ -228,11 +240,21 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
       l_run[st] = l_run[st] * alpha + psum;
 
       // ---- write P (bf16) into this wave's LDS tile: [q=lo][k=16t+4hi+r] -
+      // DROP: the four 16-key tiles are one quad exchange; query q_idx, keys
+      // kv0 + 16t + 4hi + r
+      unsigned du[4];
+      if constexpr (DROP)
+        attn_drop_u<4, false>(dkey, drop.site, (unsigned)bh, (unsigned)q_idx >> 2, 0,
+                              (unsigned)(kv0 >> 2) + hi, 4, lo & 3, du);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         bf16x4 pk;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) pk[r] = f2bfs(sv[4 * t + r]);
+        for (int r = 0; r < 4; ++r) {
+          pk[r] = f2bfs(sv[4 * t + r]);
+          if constexpr (DROP)
+            if (!attn_keep(du[t], r, drop.thresh)) pk[r] = 0;
+        }
         *reinterpret_cast<bf16x4*>(my_p + lo * LDS_PITCH + 16 * t + hi * 4) = pk;
       }
 
@@ -268,7 +290,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const int ti = blockIdx.x + st * gridDim.x;
     const int q0 = ti * QBLK + wave * 16;
     if (ti >= ntq || q0 >= Lq) continue;
-    const float invl = (l_run[st] > 0.f) ? 1.f / l_run[st] : 0.f;
+    float invl = (l_run[st] > 0.f) ? 1.f / l_run[st] : 0.f;
+    if constexpr (DROP) invl *= drop.scale;
     float invl_r[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) invl_r[r] = __shfl(invl, hi * 4 + r, WAVE);
@@ -495,11 +518,11 @@ __global__ __launch_bounds__(320) void attn_fwd_small_kernel(
 // ds_read_b64_tr_b16.
 // ---------------------------------------------------------------------------
 
-template <int NBLK>
+template <int NBLK, bool DROP = false>
 __global__ __launch_bounds__(512, 4) void attn_fwd_resident_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     bf16* __restrict__ o, float* __restrict__ lse, int L, float scale, int H, hstride q_s,
-    hstride k_s, hstride v_s, hstride o_s) {
+    hstride k_s, hstride v_s, hstride o_s, drop_args drop = {}) {
   constexpr int D = 64;
   constexpr int LP = 32 * NBLK;  // image rows: whole 32-row blocks
   constexpr int IMG = LP * D;
@@ -543,6 +566,8 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_resident_kernel(
   __syncthreads();
 
   const float c = scale * 1.44269504088896340736f;  // scores in log2 units
+  drop_key dkey = {};
+  if constexpr (DROP) dkey = load_drop_key(drop);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int s0 = 16 * (wave + i * NBLK);
@@ -580,7 +605,8 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_resident_kernel(
         for (int r = 0; r < 4; ++r) {
           float x = sc[kb][t][r] * c;
           if (kb == NBLK - 1 && 32 * kb + 16 * t + 4 * hi + r >= L) x = -INFINITY;
-          sc[kb][t][r] = x;
+          // DROP keeps the raw score of the unmasked blocks for its fma below
+          if (!DROP || kb == NBLK - 1) sc[kb][t][r] = x;
           m = fmaxf(m, x);
         }
       }
@@ -592,16 +618,37 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_resident_kernel(
     // ---- P = exp2(S - m) 32 keys at a time; O^T += V^T . P^T -----------------
     float lsum = 0.f;
     f32x4 acc[4] = {};
+    unsigned du[4];  // DROP: one quad exchange per two key blocks (four 16-key tiles)
 #pragma unroll
     for (int kb = 0; kb < NBLK; ++kb) {
+      if constexpr (DROP)
+        if ((kb & 1) == 0)  // query s0 + lo, keys 32kb + 16g + 4hi + r, g < 4
+          attn_drop_u<4, false>(dkey, drop.site, (unsigned)bh, (unsigned)(s0 + lo) >> 2, 0,
+                                8 * kb + hi, 4, lo & 3, du);
       bf16x8 pf;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float p = __builtin_amdgcn_exp2f(sc[kb][t][r] - msub);
+          // The DROP-off kernels compile (sc * c) - msub to one fma on the raw
+          // score in every block but the last, whose masked product is rounded
+          // first. DROP writes that rounding out instead of leaving it to
+          // contraction, which chose otherwise here: P, the row sum and lse
+          // are then bit for bit those of the same call at p = 0.
+          float e;
+          if constexpr (!DROP) {
+            e = sc[kb][t][r] - msub;
+          } else if (kb < NBLK - 1) {
+            e = __builtin_fmaf(sc[kb][t][r], c, -msub);
+          } else {
+#pragma clang fp contract(off)
+            e = sc[kb][t][r] - msub;
+          }
+          const float p = __builtin_amdgcn_exp2f(e);
           lsum += p;
           pf[4 * t + r] = f2bfs(p);
+          if constexpr (DROP)
+            if (!attn_keep(du[2 * (kb & 1) + t], r, drop.thresh)) pf[4 * t + r] = 0;
         }
       }
       bf16x8 vfr[4];
@@ -616,7 +663,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_resident_kernel(
 
     // acc holds O^T tiles: lane = query lo, d = 16dt + 4hi + r -> 8-byte stores
     if (sok) {
-      const float invl = 1.f / lsum;
+      const float invl = (DROP ? drop.scale : 1.f) / lsum;
       bf16* op = head_ptr(o, o_s, bh, H) + (int64_t)(s0 + lo) * o_s.l + 4 * hi;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
@@ -625,15 +672,56 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_resident_kernel(
         for (int r = 0; r < 4; ++r) pk[r] = f2bfs(acc[dt][r] * invl);
         *reinterpret_cast<bf16x4*>(op + 16 * dt) = pk;
       }
-      if (hi == 0) lse[bh * L + s0 + lo] = m * 0.69314718055994530942f + __logf(lsum);
+      if (hi == 0)
+        lse[bh * L + s0 + lo] = __builtin_fmaf(m, 0.69314718055994530942f, __logf(lsum));
     }
   }
 }
 
 }  // namespace
 
+// Launch of the DROP instantiations (non-causal; resident inside the resident
+// domain, else tiled at any L). They are compiled in attention_drop.hip, which
+// includes this file with packed fp32 arithmetic off; attn_fwd below stays the
+// one front end and has checked every argument.
+void attn_fwd_drop(const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
+                   const torch::Tensor& o, const torch::Tensor& lse, double scale, bool resident,
+                   const drop_args& drop)
+#ifdef JIMM_ATTN_DROP_TU
+{
+  const int Dr = q.size(3);
+  const int DP = Dr <= 64 ? 64 : (Dr <= 96 ? 96 : 128);
+  const int H = q.size(1), Lq = q.size(2), Lk = k.size(2);
+  const unsigned BH = (unsigned)(q.size(0) * q.size(1));
+  auto stream = at::hip::getCurrentHIPStream();
+  if (resident) {
+    const int nblk = (Lk + 31) / 32;
+    const size_t rshmem = (size_t)2 * nblk * 32 * 64 * sizeof(short);
+    constexpr size_t rshmem_max = (size_t)2 * RES_LMAX * 64 * sizeof(short);
+    with_int<3, 4, 5, 6, 7, 8>(nblk, "resident block count", [&](auto nb) {
+      launch_lds<attn_fwd_resident_kernel<decltype(nb)::value, true>>(
+          dim3(BH), dim3(nblk * WAVE), rshmem, rshmem_max, stream, bf16_ptr(q), bf16_ptr(k),
+          bf16_ptr(v), bf16_ptr(o), lse.data_ptr<float>(), Lk, (float)scale, H, hstrides(q),
+          hstrides(k), hstrides(v), hstrides(o), drop);
+    });
+    return;
+  }
+  const int ntq = (Lq + QBLK - 1) / QBLK;
+  const size_t shmem =
+      (2 * (KVBLK * DP + KVBLK * (DP + 8)) + 4 * 16 * (DP + 8)) * sizeof(short);
+  with_int<64, 96, 128>(DP, "padded head dim", [&](auto dp) {
+    launch_lds<attn_fwd_kernel<false, decltype(dp)::value, true>>(
+        dim3((ntq + NSTRIP - 1) / NSTRIP, BH), dim3(256), shmem, shmem, stream, bf16_ptr(q),
+        bf16_ptr(k), bf16_ptr(v), bf16_ptr(o), lse.data_ptr<float>(), Lq, Lk, (float)scale, H, Dr,
+        hstrides(q), hstrides(k), hstrides(v), hstrides(o), drop);
+  });
+}
+#else
+;
+
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                                    bool causal, double scale, std::string path) {
+                                    bool causal, double scale, std::string path, double p,
+                                    c10::optional<torch::Tensor> rng, int64_t site) {
   // q,k,v: (B,H,L,D) views whose innermost dim is contiguous — covers both
   // contiguous BHLD and the un-copied (B,L,H,D) / fused-qkv (B,L,3,H,D)
   // layouts.
@@ -646,6 +734,9 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
   // its domain
   TORCH_CHECK(path == "auto" || path == "tiled" || path == "resident",
               "attn_fwd: path must be auto, tiled or resident, got ", path);
+  // attention-probability dropout: t8 == 0 is today's path, untouched
+  const unsigned t8 = attn_drop_threshold(p);
+  check_attn_drop("attn_fwd", t8, causal, Lq, Lk);
   const bool aligned = res_aligned({&q, &k, &v});  // o is allocated below, aligned
   const bool resident_ok = Dr == 64 && Lq == Lk && !causal && Lk >= RES_LMIN &&
                            Lk <= RES_LMAX && aligned;
@@ -659,6 +750,11 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
   auto lse = torch::empty({B, H, Lq}, q.options().dtype(torch::kFloat32));
   const unsigned BH = (unsigned)((int64_t)B * H);
   auto stream = at::hip::getCurrentHIPStream();
+  if (t8 > 0) {
+    attn_fwd_drop(q, k, v, o, lse, scale, path != "tiled" && resident_ok,
+                  make_attn_drop_args(t8, rng, site, q));
+    return {o, lse};
+  }
   if (path != "tiled" && resident_ok) {
     // one wave per 32 rows (two 16-row strips each); K and V images only.
     // The LDS limit is raised once, to the largest supported L.
@@ -669,7 +765,7 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
       launch_lds<attn_fwd_resident_kernel<decltype(nb)::value>>(
           dim3(BH), dim3(nblk * WAVE), rshmem, rshmem_max, stream, bf16_ptr(q), bf16_ptr(k),
           bf16_ptr(v), bf16_ptr(o), lse.data_ptr<float>(), Lk, (float)scale, H, hstrides(q),
-          hstrides(k), hstrides(v), hstrides(o));
+          hstrides(k), hstrides(v), hstrides(o), drop_args{});
     });
     return {o, lse};
   }
@@ -692,9 +788,11 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
           launch_lds<attn_fwd_kernel<C, decltype(dp)::value>>(
               dim3((ntq + NSTRIP - 1) / NSTRIP, BH), dim3(256), shmem, shmem, stream,
               bf16_ptr(q), bf16_ptr(k), bf16_ptr(v), bf16_ptr(o), lse.data_ptr<float>(), Lq, Lk,
-              (float)scale, H, Dr, hstrides(q), hstrides(k), hstrides(v), hstrides(o));
+              (float)scale, H, Dr, hstrides(q), hstrides(k), hstrides(v), hstrides(o),
+              drop_args{});
         });
       },
       causal);
   return {o, lse};
 }
+#endif  // JIMM_ATTN_DROP_TU

@@ -19,6 +19,19 @@
 //   attn_bwd_resident_kernel — 81 <= Lq == Lk <= 256, non-causal (ViT-B L=197)
 // (both D = 64; see their header comments and the dispatch in attn_bwd_fused).
 //
+// Attention-probability dropout (template flag DROP of the tiled pair and the
+// resident kernel; mask and call sharing in common.h, attn_drop_u). With keep
+// mask m and s = 1 / keep rate the forward was O = ((P o m) s) V, so
+//   dP = (dO V^T) o m * s, dS = P o (dP - delta), dV = ((P o m) s)^T dO,
+// with delta = rowsum(dO o O) over the dropped O (attn_d2_kernel and the
+// resident kernel's own sweep, unchanged). Where s goes: onto the fp32 dP
+// value of a kept element (one multiply by 0 or s in front of - delta), and
+// onto the final dV accumulators; the bf16 P fragment of the dV MFMA is
+// P o m, a zeroed entry per dropped element, as in the forward. The tiled
+// kernels exchange four tiles per quad (a quarter of a Philox call per lane
+// and tile); the resident kernel's run-time block loops exchange the two
+// tiles of one 32-row block (half a call). No small-L and no causal form.
+//
 // All tensor arguments are (B,H,L,64) *views* with arbitrary (b,h,l) strides
 // and a contiguous innermost dim — q/k/v slices of the fused (B,L,3,H,64)
 // QKV projection and (B,L,H,64)-storage dO/O are consumed with zero permute
@@ -90,12 +103,14 @@ __global__ void attn_d2_kernel(const bf16* __restrict__ dO, const bf16* __restri
 // dK/dV kernel: workgroup owns keys [kv0, kv0+64); loops q tiles
 // ---------------------------------------------------------------------------
 
-template <bool CAUSAL, int DP>
+template <bool CAUSAL, int DP, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     const bf16* __restrict__ dO, const float* __restrict__ lse, const float* __restrict__ Dv,
     bf16* __restrict__ dk, bf16* __restrict__ dv, int Lq, int Lk, float scale, int H,
-    int Dr, hstride q_s, hstride k_s, hstride v_s, hstride do_s, hstride dk_s, hstride dv_s) {
+    int Dr, hstride q_s, hstride k_s, hstride v_s, hstride do_s, hstride dk_s, hstride dv_s,
+    drop_args drop = {}) {
+  static_assert(!(DROP && CAUSAL), "no causal dropout form");
   // Each workgroup owns up to NKV kv tiles (cyclic tile mapping, like the
   // forward kernel) so the Q/dO images are staged ONCE for all of them (one
   // kv tile per workgroup is 4x redundant staging at L=197).
@@ -153,6 +168,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
   }
 
   short* my_p = p_lds + wave * 16 * PITCH;
+  drop_key dkey = {};
+  if constexpr (DROP) dkey = load_drop_key(drop);
 
   f32x4 acc_dk[NKV][NT] = {};  // rows key = 16*wave + hi*4+r, cols d = 16*dt+lo
   f32x4 acc_dv[NKV][NT] = {};
@@ -242,6 +259,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
       // at L=197): every P/dS is zero and the dK/dV stores are key-guarded —
       // skip the strip's S/P/dS and MFMA work outright
       if (key_min >= Lk) continue;
+      // DROP: the four 16-query tiles are one quad exchange; query
+      // q0 + 16qt + lo, keys key_min + 4hi + r
+      unsigned du[4];
+      if constexpr (DROP)
+        attn_drop_u<4, false>(dkey, drop.site, (unsigned)bh, (unsigned)(q0 + lo) >> 2, 4,
+                              (unsigned)(key_min >> 2) + hi, 0, lo & 3, du);
       bf16x4 ds_stash[4];
 #pragma unroll
       for (int qt = 0; qt < 4; ++qt) {
@@ -281,7 +304,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
           float p = __expf(sc[r] * scale - l);
           if (qi >= Lq || key >= Lk || (CAUSAL && key > qi)) p = 0.f;
           pk[r] = f2bfs(p);
-          dsk[r] = f2bfs(p * (dpc[r] - dcoef) * scale);
+          if constexpr (DROP) {
+            const bool keep = attn_keep(du[qt], r, drop.thresh);
+            if (!keep) pk[r] = 0;
+            dsk[r] = f2bfs(p * (dpc[r] * (keep ? drop.scale : 0.f) - dcoef) * scale);
+          } else {
+            dsk[r] = f2bfs(p * (dpc[r] - dcoef) * scale);
+          }
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) my_p[(hi * 4 + r) * PITCH + 16 * qt + lo] = pk[r];
@@ -339,7 +368,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
       for (int dt = 0; dt < NT; ++dt) {
         if (DP != 64 && 16 * dt + lo >= Dr) continue;
         dkp[(int64_t)key * dk_s.l + 16 * dt + lo] = f2bf(acc_dk[sidx][dt][r]);
-        dvp[(int64_t)key * dv_s.l + 16 * dt + lo] = f2bf(acc_dv[sidx][dt][r]);
+        dvp[(int64_t)key * dv_s.l + 16 * dt + lo] =
+            f2bf(DROP ? acc_dv[sidx][dt][r] * drop.scale : acc_dv[sidx][dt][r]);
       }
     }
   }
@@ -349,12 +379,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
 // dQ kernel: workgroup owns q rows [q0, q0+64); loops kv tiles
 // ---------------------------------------------------------------------------
 
-template <bool CAUSAL, int DP>
+template <bool CAUSAL, int DP, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     const bf16* __restrict__ dO, const float* __restrict__ lse, const float* __restrict__ Dv,
     bf16* __restrict__ dq, int Lq, int Lk, float scale, int H, int Dr, hstride q_s,
-    hstride k_s, hstride v_s, hstride do_s, hstride dq_s) {
+    hstride k_s, hstride v_s, hstride do_s, hstride dq_s, drop_args drop = {}) {
+  static_assert(!(DROP && CAUSAL), "no causal dropout form");
   // Each workgroup owns up to NQS q tiles (cyclic mapping) so the K images
   // are staged ONCE for all of them; Q/dO A-fragments live in registers per
   // strip. LDS: K^T + K/V row images of the current kv tile, per-wave dS
@@ -413,6 +444,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
   }
 
   short* my_ds = ds_lds + wave * 16 * PITCH;
+  drop_key dkey = {};
+  if constexpr (DROP) dkey = load_drop_key(drop);
   f32x4 acc_dq[NQS][NT] = {};  // rows q = hi*4+r, cols d = 16*dt + lo
 
   // causal: only kv tiles up to the LAST active strip's diagonal are needed
@@ -492,6 +525,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
       // key sub-tiles above this strip's causal diagonal or beyond Lk give
       // dS = 0: write zeros, skip the MFMAs
       const int q_max = q0s + 15;
+      // DROP: the four 16-key tiles are one quad exchange; key
+      // kv0 + 16kt + lo, queries q0s + 4hi + r
+      unsigned du[4];
+      if constexpr (DROP)
+        attn_drop_u<4, true>(dkey, drop.site, (unsigned)bh, (unsigned)(q0s >> 2) + hi, 0,
+                             (unsigned)(kv0 + lo) >> 2, 4, lo & 3, du);
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
         const bool skip_kt =
@@ -525,7 +564,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
           const int qi = q0s + hi * 4 + r;
           float p = __expf(sc[r] * scale - lse_r[sidx][r]);
           if (key >= Lk || (CAUSAL && key > qi)) p = 0.f;
-          dsk[r] = f2bfs(p * (dpc[r] - d_r[sidx][r]) * scale);
+          float dp = dpc[r];
+          if constexpr (DROP) dp *= attn_keep(du[kt], r, drop.thresh) ? drop.scale : 0.f;
+          dsk[r] = f2bfs(p * (dp - d_r[sidx][r]) * scale);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) my_ds[(hi * 4 + r) * PITCH + 16 * kt + lo] = dsk[r];
@@ -816,14 +857,17 @@ __global__ __launch_bounds__(320) void attn_bwd_small_kernel(
 // resident forward, attention.hip).
 // ---------------------------------------------------------------------------
 
+template <bool DROP = false>
 __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     const bf16* __restrict__ o, const bf16* __restrict__ dO, const float* __restrict__ lse,
     bf16* __restrict__ dq, bf16* __restrict__ dk, bf16* __restrict__ dv, int L, float scale,
     int H, hstride q_s, hstride k_s, hstride v_s, hstride o_s, hstride do_s, hstride dq_s,
-    hstride dk_s, hstride dv_s) {
+    hstride dk_s, hstride dv_s, drop_args drop = {}) {
   constexpr int D = 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  drop_key dkey = {};
+  if constexpr (DROP) dkey = load_drop_key(drop);
   const int LP = (L + 31) & ~31;  // image rows: whole 32-row blocks
   const int IMG = LP * D;
   short* imgA = reinterpret_cast<short*>(smem);  // K, then Q
@@ -916,6 +960,10 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
         __builtin_amdgcn_s_setprio(0);
       }
       bf16x8 dsa;
+      unsigned du[2];  // DROP: query s0 + lo, keys 32kb + 16t + 4hi + r
+      if constexpr (DROP)
+        attn_drop_u<2, false>(dkey, drop.site, (unsigned)bh, (unsigned)(s0 + lo) >> 2, 0,
+                              8 * kb + hi, 4, lo & 3, du);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
@@ -923,7 +971,9 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
           const int key = 32 * kb + 16 * t + 4 * hi + r;
           const bool ok = sok && key < L;
           const float p = ok ? __expf(sc[t][r] * scale - lse_q) : 0.f;
-          const float ds = ok ? p * (dpc[t][r] - dli) * scale : 0.f;
+          float dp = dpc[t][r];
+          if constexpr (DROP) dp *= attn_keep(du[t], r, drop.thresh) ? drop.scale : 0.f;
+          const float ds = ok ? p * (dp - dli) * scale : 0.f;
           dsa[4 * t + r] = f2bfs(ds);
         }
       }
@@ -1009,6 +1059,10 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
         __builtin_amdgcn_s_setprio(0);
       }
       bf16x8 pa, dsa;
+      unsigned du[2];  // DROP: key s0 + lo, queries 32qblk + 16t + 4hi + r
+      if constexpr (DROP)
+        attn_drop_u<2, true>(dkey, drop.site, (unsigned)bh, 8 * qblk + hi, 4,
+                             (unsigned)(s0 + lo) >> 2, 0, lo & 3, du);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int qi0 = 32 * qblk + 16 * t + 4 * hi;
@@ -1018,8 +1072,14 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
         for (int r = 0; r < 4; ++r) {
           const bool ok = sok && qi0 + r < L;
           const float p = ok ? __expf(sc[t][r] * scale - ls4[r]) : 0.f;
-          const float ds = ok ? p * (dpc[t][r] - dl4[r]) * scale : 0.f;
-          pa[4 * t + r] = f2bfs(p);
+          float dp = dpc[t][r];
+          bool keep = true;
+          if constexpr (DROP) {
+            keep = attn_keep(du[t], r, drop.thresh);
+            dp *= keep ? drop.scale : 0.f;
+          }
+          const float ds = ok ? p * (dp - dl4[r]) * scale : 0.f;
+          pa[4 * t + r] = keep ? f2bfs(p) : (short)0;
           dsa[4 * t + r] = f2bfs(ds);
         }
       }
@@ -1045,7 +1105,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           pk[r] = f2bfs(adk[dt][r]);
-          pv[r] = f2bfs(adv[dt][r]);
+          pv[r] = f2bfs(DROP ? adv[dt][r] * drop.scale : adv[dt][r]);
         }
         *reinterpret_cast<bf16x4*>(dkp + 16 * dt) = pk;
         *reinterpret_cast<bf16x4*>(dvp + 16 * dt) = pv;
@@ -1056,9 +1116,67 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
 
 }  // namespace
 
+// Launch of the DROP instantiations (non-causal; resident inside the resident
+// domain, else d2 + the tiled pair at any L). They are compiled in
+// attention_drop.hip, which includes this file with packed fp32 arithmetic
+// off; attn_bwd_fused below stays the one front end and has checked every
+// argument.
+void attn_bwd_drop(const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
+                   const torch::Tensor& o, const torch::Tensor& dO, const torch::Tensor& lse,
+                   const torch::Tensor& dq, const torch::Tensor& dk, const torch::Tensor& dv,
+                   double scale, bool resident, const drop_args& drop)
+#ifdef JIMM_ATTN_DROP_TU
+{
+  const int Dr = q.size(3);
+  const int DP = Dr <= 64 ? 64 : (Dr <= 96 ? 96 : 128);
+  const int B = q.size(0), H = q.size(1), Lq = q.size(2), Lk = k.size(2);
+  const unsigned BH = (unsigned)((int64_t)B * H);
+  auto stream = at::hip::getCurrentHIPStream();
+  if (resident) {
+    const int LP = (Lk + 31) & ~31;
+    const size_t rshmem = (size_t)2 * LP * 64 * sizeof(short) + (size_t)2 * LP * sizeof(float);
+    constexpr size_t rshmem_max =
+        (size_t)2 * RES_LMAX * 64 * sizeof(short) + (size_t)2 * RES_LMAX * sizeof(float);
+    launch_lds<attn_bwd_resident_kernel<true>>(
+        dim3(BH), dim3(LP / 32 * WAVE), rshmem, rshmem_max, stream, bf16_ptr(q), bf16_ptr(k),
+        bf16_ptr(v), bf16_ptr(o), bf16_ptr(dO), lse.data_ptr<float>(), bf16_ptr(dq),
+        bf16_ptr(dk), bf16_ptr(dv), Lk, (float)scale, H, hstrides(q), hstrides(k), hstrides(v),
+        hstrides(o), hstrides(dO), hstrides(dq), hstrides(dk), hstrides(dv), drop);
+    return;
+  }
+  auto Dv = torch::empty({(int64_t)B * H * Lq}, q.options().dtype(torch::kFloat32));
+  const int64_t nrows = (int64_t)B * H * Lq;
+  const dim3 grid((unsigned)std::min<int64_t>((nrows + 3) / 4, 4096));
+  hipLaunchKernelGGL(attn_d2_kernel, grid, dim3(256), 0, stream, bf16_ptr(dO), bf16_ptr(o),
+                     Dv.data_ptr<float>(), H, Lq, Dr, nrows, hstrides(dO), hstrides(o));
+  const int pitch = DP + 8;
+  const size_t shmem_dkv =
+      (2 * (2 * BLK * DP + 2 * BLK * pitch) + 4 * 16 * pitch) * sizeof(short);
+  const size_t shmem_dq = (2 * (BLK * DP + 2 * BLK * pitch) + 4 * 16 * pitch) * sizeof(short);
+  const int ntk = (Lk + BLK - 1) / BLK;
+  const int ntq = (Lq + BLK - 1) / BLK;
+  const int tpw = tiles_per_wg(DP);
+  with_int<64, 96, 128>(DP, "padded head dim", [&](auto dp) {
+    constexpr int P = decltype(dp)::value;
+    launch_lds<attn_bwd_dkv_kernel<false, P, true>>(
+        dim3((ntk + tpw - 1) / tpw, BH), dim3(256), shmem_dkv, shmem_dkv, stream, bf16_ptr(q),
+        bf16_ptr(k), bf16_ptr(v), bf16_ptr(dO), lse.data_ptr<float>(), Dv.data_ptr<float>(),
+        bf16_ptr(dk), bf16_ptr(dv), Lq, Lk, (float)scale, H, Dr, hstrides(q), hstrides(k),
+        hstrides(v), hstrides(dO), hstrides(dk), hstrides(dv), drop);
+    launch_lds<attn_bwd_dq_kernel<false, P, true>>(
+        dim3((ntq + tpw - 1) / tpw, BH), dim3(256), shmem_dq, shmem_dq, stream, bf16_ptr(q),
+        bf16_ptr(k), bf16_ptr(v), bf16_ptr(dO), lse.data_ptr<float>(), Dv.data_ptr<float>(),
+        bf16_ptr(dq), Lq, Lk, (float)scale, H, Dr, hstrides(q), hstrides(k), hstrides(v),
+        hstrides(dO), hstrides(dq), drop);
+  });
+}
+#else
+;
+
 void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o,
                     torch::Tensor dO, torch::Tensor lse, torch::Tensor dq, torch::Tensor dk,
-                    torch::Tensor dv, bool causal, double scale, std::string path) {
+                    torch::Tensor dv, bool causal, double scale, std::string path, double p,
+                    c10::optional<torch::Tensor> rng, int64_t site) {
   // all tensors (B,H,L,D) views, innermost contiguous, arbitrary b/h/l strides
   check_attn_args("attn_bwd_fused", {{"q", q}, {"o", o}, {"dO", dO}, {"dq", dq}},
                   {{"k", k}, {"v", v}, {"dk", dk}, {"dv", dv}}, &lse);
@@ -1079,6 +1197,14 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
               "attn_bwd_fused: path=resident needs D == 64, Lq == Lk, non-causal, ",
               RES_LMIN, " <= L <= ", RES_LMAX, " and 16-byte aligned rows; got D=", Dr,
               " Lq=", Lq, " Lk=", Lk, " causal=", causal, " aligned=", aligned);
+  // attention-probability dropout: t8 == 0 is today's path, untouched
+  const unsigned t8 = attn_drop_threshold(p);
+  check_attn_drop("attn_bwd_fused", t8, causal, Lq, Lk);
+  if (t8 > 0) {
+    attn_bwd_drop(q, k, v, o, dO, lse, dq, dk, dv, scale, path != "tiled" && resident_ok,
+                  make_attn_drop_args(t8, rng, site, q));
+    return;
+  }
   if (path != "tiled" && resident_ok) {
     // one wave per 32 rows (two 16-row strips each); two images + lse + delta
     const int LP = (Lk + 31) & ~31;
@@ -1086,11 +1212,11 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
     // the LDS limit is raised once, to the largest supported L
     constexpr size_t rshmem_max =
         (size_t)2 * RES_LMAX * 64 * sizeof(short) + (size_t)2 * RES_LMAX * sizeof(float);
-    launch_lds<attn_bwd_resident_kernel>(
+    launch_lds<attn_bwd_resident_kernel<>>(
         dim3(BH), dim3(LP / 32 * WAVE), rshmem, rshmem_max, stream, bf16_ptr(q), bf16_ptr(k),
         bf16_ptr(v), bf16_ptr(o), bf16_ptr(dO), lse.data_ptr<float>(), bf16_ptr(dq),
         bf16_ptr(dk), bf16_ptr(dv), Lk, (float)scale, H, hstrides(q), hstrides(k), hstrides(v),
-        hstrides(o), hstrides(dO), hstrides(dq), hstrides(dk), hstrides(dv));
+        hstrides(o), hstrides(dO), hstrides(dq), hstrides(dk), hstrides(dv), drop_args{});
     return;
   }
 
@@ -1134,13 +1260,15 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
               dim3((ntk + tpw - 1) / tpw, BH), dim3(256), shmem_dkv, shmem_dkv, stream,
               bf16_ptr(q), bf16_ptr(k), bf16_ptr(v), bf16_ptr(dO), lse.data_ptr<float>(),
               Dv.data_ptr<float>(), bf16_ptr(dk), bf16_ptr(dv), Lq, Lk, (float)scale, H, Dr,
-              hstrides(q), hstrides(k), hstrides(v), hstrides(dO), hstrides(dk), hstrides(dv));
+              hstrides(q), hstrides(k), hstrides(v), hstrides(dO), hstrides(dk), hstrides(dv),
+              drop_args{});
           launch_lds<attn_bwd_dq_kernel<C, P>>(
               dim3((ntq + tpw - 1) / tpw, BH), dim3(256), shmem_dq, shmem_dq, stream,
               bf16_ptr(q), bf16_ptr(k), bf16_ptr(v), bf16_ptr(dO), lse.data_ptr<float>(),
               Dv.data_ptr<float>(), bf16_ptr(dq), Lq, Lk, (float)scale, H, Dr, hstrides(q),
-              hstrides(k), hstrides(v), hstrides(dO), hstrides(dq));
+              hstrides(k), hstrides(v), hstrides(dO), hstrides(dq), drop_args{});
         });
       },
       causal);
 }
+#endif  // JIMM_ATTN_DROP_TU

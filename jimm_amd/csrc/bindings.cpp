@@ -42,13 +42,15 @@ void adam_apply_clipped(torch::Tensor desc, int64_t nchunks, torch::Tensor lr_de
                         double eps, double wd);
 void grad_scale(torch::Tensor desc, int64_t nchunks, torch::Tensor stats);
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                                    bool causal, double scale, std::string path);
+                                    bool causal, double scale, std::string path, double p,
+                                    c10::optional<torch::Tensor> rng, int64_t site);
 void attn_bwd_p(torch::Tensor s, torch::Tensor lse, bool causal, double scale);
 torch::Tensor attn_d(torch::Tensor dO, torch::Tensor O);
 void attn_ds(torch::Tensor dp, torch::Tensor p, torch::Tensor D, double scale);
 void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o,
                     torch::Tensor dO, torch::Tensor lse, torch::Tensor dq, torch::Tensor dk,
-                    torch::Tensor dv, bool causal, double scale, std::string path);
+                    torch::Tensor dv, bool causal, double scale, std::string path, double p,
+                    c10::optional<torch::Tensor> rng, int64_t site);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
 torch::Tensor mfma_probe32(torch::Tensor A, torch::Tensor B);
 bool gemm_supported(int64_t M, int64_t N, int64_t K, std::string dtype);
@@ -144,17 +146,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "adam_apply with g scaled by the device clip coefficient; skips on a non-finite norm");
   m.def("grad_scale", &grad_scale, "in-place g *= device clip coefficient (K14 clipping)");
   m.def("attn_fwd", &attn_fwd,
-        "flash attention forward (K5); path: auto | tiled | resident",
+        "flash attention forward (K5); path: auto | tiled | resident; p > 0 drops "
+        "attention probabilities at `site`",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),
-        py::arg("path") = "auto");
+        py::arg("path") = "auto", py::arg("p") = 0.0, py::arg("rng") = py::none(),
+        py::arg("site") = 0);
   m.def("attn_bwd_p", &attn_bwd_p, "attention bwd: S -> P in place (K15)");
   m.def("attn_d", &attn_d, "attention bwd: rowsum(dO*O) (K15)");
   m.def("attn_ds", &attn_ds, "attention bwd: dP -> dS in place (K15)");
   m.def("attn_bwd_fused", &attn_bwd_fused,
-        "fused flash attention backward (K15); path: auto | tiled | resident",
+        "fused flash attention backward (K15); path: auto | tiled | resident; p, rng, site "
+        "as given to attn_fwd",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dO"), py::arg("lse"),
         py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal"), py::arg("scale"),
-        py::arg("path") = "auto");
+        py::arg("path") = "auto", py::arg("p") = 0.0, py::arg("rng") = py::none(),
+        py::arg("site") = 0);
   m.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 layout probe");
   m.def("mfma_probe32", &mfma_probe32, "MFMA 32x32x16 layout probe");
   m.def("gemm_supported", &gemm_supported, "MFMA GEMM shape support check");

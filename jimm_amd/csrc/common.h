@@ -238,6 +238,73 @@ inline drop_args make_drop_args(unsigned t, const c10::optional<torch::Tensor>& 
           (float)(65536.0 / (65536.0 - (double)t))};
 }
 
+// ---- attention-probability dropout (ops/philox_dropout.py, attn_keep_mask) ----
+// Element (i, j) = (query, key) of head bh reads counter
+// {bh, (i >> 2) | ((j >> 2) << 16), site, step}, key {seed lo, seed hi}, word
+// i & 3 and byte j & 3 of that word: u8. Keep iff u8 >= t8 = min(round(256 p),
+// 255); s = 256 / (256 - t8). One call serves the 4 x 4 block (i >> 2, j >> 2),
+// and the definition knows nothing of a kernel's tiles. drop_args carries it
+// with thresh = t8 and scale = s.
+//
+// In every aligned 16 x 16 MFMA accumulator tile a lane (lo, hi) owns 4
+// consecutive keys of one query (S^T tiles: query = lane lo) or 4 consecutive
+// queries of one key (S tiles: key = lane lo), so the DPP quad lo = 4a .. 4a+3
+// of one hi owns exactly one block. attn_drop_u serves G tiles at once whose
+// blocks are (ib0 + t * ibs, jb0 + t * jbs), t < G: lane c = lo & 3 makes the
+// ONE call of tile c % G, and tile t's four words are broadcast from lane t
+// of the quad (quad_perm moves, no LDS). With G = 4 that is a quarter of a
+// call per lane and tile, with G = 2 half of one. u[t] holds the lane's four
+// uniforms of tile t, byte r for its r-th element (key 4hi + r of its query,
+// or query 4hi + r of its key: KEYLANE). Call it with all 64 lanes active.
+template <int T>
+__device__ __forceinline__ unsigned quad_bcast(unsigned x) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, T * 0x55, 0xf, 0xf, false);
+}
+
+template <int G, bool KEYLANE>
+__device__ __forceinline__ void attn_drop_u(const drop_key& k, unsigned site, unsigned bh,
+                                            unsigned ib0, unsigned ibs, unsigned jb0, unsigned jbs,
+                                            unsigned c, unsigned (&u)[G]) {
+  static_assert(G == 2 || G == 4, "tiles per quad exchange");
+  const unsigned mine = c & (G - 1);
+  unsigned w[4];
+  philox4x32_10(bh, (ib0 + mine * ibs) | ((jb0 + mine * jbs) << 16), site, k.step, k.k0, k.k1, w);
+  auto pick = [&](unsigned x0, unsigned x1, unsigned x2, unsigned x3) {
+    if (KEYLANE) {  // byte c of every word: queries 0..3 of the block, this lane's key
+      const unsigned sh = 8 * c;
+      return ((x0 >> sh) & 0xffu) | (((x1 >> sh) & 0xffu) << 8) | (((x2 >> sh) & 0xffu) << 16) |
+             (((x3 >> sh) & 0xffu) << 24);
+    }
+    return c == 0 ? x0 : c == 1 ? x1 : c == 2 ? x2 : x3;  // word c: this lane's query
+  };
+  u[0] = pick(quad_bcast<0>(w[0]), quad_bcast<0>(w[1]), quad_bcast<0>(w[2]), quad_bcast<0>(w[3]));
+  u[1] = pick(quad_bcast<1>(w[0]), quad_bcast<1>(w[1]), quad_bcast<1>(w[2]), quad_bcast<1>(w[3]));
+  if constexpr (G == 4) {
+    u[2] = pick(quad_bcast<2>(w[0]), quad_bcast<2>(w[1]), quad_bcast<2>(w[2]), quad_bcast<2>(w[3]));
+    u[3] = pick(quad_bcast<3>(w[0]), quad_bcast<3>(w[1]), quad_bcast<3>(w[2]), quad_bcast<3>(w[3]));
+  }
+}
+
+// Element r's keep decision from a word of attn_drop_u.
+__device__ __forceinline__ bool attn_keep(unsigned u, int r, unsigned t8) {
+  return ((u >> (8 * r)) & 0xffu) >= t8;
+}
+
+// Host: t8 = min(round(p * 256), 255), halves up (attn_dropout_threshold).
+inline unsigned attn_drop_threshold(double p) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout probability must be in [0, 1), got ", p);
+  const double t = std::floor(p * 256.0 + 0.5);
+  return t > 255.0 ? 255u : (unsigned)t;
+}
+
+// Host: kernel arguments of an attention dropout with threshold t8 > 0.
+inline drop_args make_attn_drop_args(unsigned t8, const c10::optional<torch::Tensor>& rng,
+                                     int64_t site, const torch::Tensor& x) {
+  drop_args d = make_drop_args(t8, rng, site, x);
+  d.scale = (float)(256.0 / (256.0 - (double)t8));
+  return d;
+}
+
 // ---- vectorized load/store helpers (G13: hipcc does not auto-vectorize
 // bf16 loads; 8-16 B per lane is the coalescing sweet spot) ----------------
 template <int V, typename T>

@@ -456,3 +456,13 @@ inline void check_attn_args(const char* op, std::initializer_list<named_tensor> 
                 op, ": lse must be contiguous fp32 (B,H,Lq)");
   }
 }
+
+// Domain of the attention-dropout kernels (t8 > 0): non-causal (CLIP's text
+// tower never uses dropout; no causal DROP instantiation exists) and row and
+// key indices that fit the mask's 16-bit block fields.
+inline void check_attn_drop(const char* op, unsigned t8, bool causal, int64_t Lq, int64_t Lk) {
+  if (t8 == 0) return;
+  TORCH_CHECK(!causal, op, ": attention dropout has no causal form");
+  TORCH_CHECK(Lq <= 262144 && Lk <= 262144, op, ": attention dropout needs L <= 262144, got Lq=",
+              Lq, " Lk=", Lk);
+}

@@ -35,6 +35,7 @@ class EncoderBlock(nn.Module):
         mlp_dim: int,
         *,
         dropout_rate: float = 0.0,
+        attention_dropout_rate: float = 0.0,
         hidden_act: str = "gelu",
         layernorm_epsilon: float = 1e-5,
         causal: bool = False,
@@ -56,6 +57,10 @@ class EncoderBlock(nn.Module):
         self.fc1 = nn.Linear(hidden_size, mlp_dim, bias=True)
         self.fc2 = nn.Linear(mlp_dim, hidden_size, bias=True)
         self.dropout = nn.Dropout(dropout_rate)  # holds p; ops.dropout does the work
+        # dropout on the attention probabilities (HF attention_probs_dropout_prob,
+        # the reference's MultiHeadAttention dropout_rate), at site
+        # ATTN_DROPOUT_SITE + site0; computed inside the flash kernels
+        self.attention_dropout_rate = attention_dropout_rate
         # dropout sites of this block: site0 after the activation, site0 + 1
         # after fc2 (an Encoder numbers its layers 2 * layer_index)
         self.site0 = 0
@@ -87,14 +92,21 @@ class EncoderBlock(nn.Module):
         (``ops.next_dropout_rng``), handed down by the Encoder so that a
         checkpoint recompute sees the same masks; a block called on its own
         draws one. Only read in training mode with dropout_rate > 0."""
+        from jimm_amd.ops.philox_dropout import ATTN_DROPOUT_SITE
+
+        p_attn = self.attention_dropout_rate if self.training else 0.0
         if getattr(self, "_tp_group", None) is not None:
+            if p_attn > 0:
+                # the local head index would repeat masks across the ranks
+                raise NotImplementedError(
+                    "attention dropout is not supported under tensor parallelism")
             return self._forward_tp(x)
         from jimm_amd.ops import block as fused
 
         # the ACTIVE dropout probability: eval of a dropout-built model is
         # the dropout-free model, fused block included
         p = self.dropout.p if self.training else 0.0
-        if p > 0 and rng is None:
+        if (p > 0 or p_attn > 0) and rng is None:
             rng = ops.next_dropout_rng(x.device)
         if (
             fused.fused_block_enabled(x, p, self.fc1.out_features)
@@ -106,13 +118,14 @@ class EncoderBlock(nn.Module):
                 x, self.norm1, self.qkv, self.proj, self.norm2, self.fc1, self.fc2,
                 num_heads=self.num_heads, act=self.act, eps=self.eps,
                 causal=self.causal, scale=1.0 / math.sqrt(self.head_dim),
-                p=p, rng=rng, site0=self.site0,
+                p=p, rng=rng, site0=self.site0, p_attn=p_attn,
             )
         B, L, H = x.shape
         h = ops.layer_norm(x, self.norm1.weight, self.norm1.bias, self.eps)
         qkv = ops.linear(h, self.qkv.weight, self.qkv.bias)  # (B, L, 3H)
         qkv = qkv.view(B, L, 3, self.num_heads, self.head_dim)
-        o = ops.attention_qkv(qkv, causal=self.causal)  # (B, heads, L, d)
+        o = ops.attention_qkv(qkv, causal=self.causal, dropout_p=p_attn, rng=rng,
+                              site=ATTN_DROPOUT_SITE + self.site0)  # (B, heads, L, d)
         o = o.transpose(1, 2).reshape(B, L, H)
         x = ops.linear(o, self.proj.weight, self.proj.bias, residual=x)
 
@@ -140,6 +153,7 @@ class Encoder(nn.Module):
         mlp_dim: int,
         *,
         dropout_rate: float = 0.0,
+        attention_dropout_rate: float = 0.0,
         hidden_act: str = "gelu",
         layernorm_epsilon: float = 1e-6,
         causal: bool = False,
@@ -151,6 +165,7 @@ class Encoder(nn.Module):
                 num_heads,
                 mlp_dim,
                 dropout_rate=dropout_rate,
+                attention_dropout_rate=attention_dropout_rate,
                 hidden_act=hidden_act,
                 layernorm_epsilon=layernorm_epsilon,
                 causal=causal,
@@ -158,6 +173,7 @@ class Encoder(nn.Module):
             for _ in range(num_layers)
         )
         self.dropout_rate = dropout_rate
+        self.attention_dropout_rate = attention_dropout_rate
         for i, layer in enumerate(self.layers):
             layer.site0 = 2 * i
 
@@ -166,7 +182,7 @@ class Encoder(nn.Module):
         # a checkpointed block's recompute replays identical masks, and a
         # second tower or a second forward draws the next step.
         rng = None
-        if self.training and self.dropout_rate > 0:
+        if self.training and (self.dropout_rate > 0 or self.attention_dropout_rate > 0):
             rng = ops.next_dropout_rng(x.device)
         if getattr(self, "gradient_checkpointing", False) and torch.is_grad_enabled():
             from torch.utils.checkpoint import checkpoint

@@ -110,6 +110,7 @@ class VisionTransformerBase(nn.Module):
         mlp_dim: int = 3072,
         *,
         dropout_rate: float = 0.0,
+        attention_dropout_rate: float = 0.0,
         use_pre_norm: bool = False,
         use_patch_bias: bool = True,
         hidden_act: str = "gelu",
@@ -155,6 +156,7 @@ class VisionTransformerBase(nn.Module):
             num_heads,
             mlp_dim,
             dropout_rate=dropout_rate,
+            attention_dropout_rate=attention_dropout_rate,
             hidden_act=hidden_act,
             layernorm_epsilon=layernorm_epsilon,
         )

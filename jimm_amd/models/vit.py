@@ -33,6 +33,8 @@ class VisionTransformer(nn.Module):
         hidden_act: str = "gelu",
         layernorm_epsilon: float = 1e-12,
         pooling: str = "CLS",  # "CLS" | "MAP" (BASELINE config 5: ViT-L/384 MAP)
+        attention_dropout_rate: float = 0.0,  # on the attention probabilities (HF
+                                              # attention_probs_dropout_prob)
     ) -> None:
         super().__init__()
         self.do_classification = do_classification
@@ -45,6 +47,7 @@ class VisionTransformer(nn.Module):
             num_heads=num_heads,
             mlp_dim=mlp_dim,
             dropout_rate=dropout_rate,
+            attention_dropout_rate=attention_dropout_rate,
             use_pre_norm=False,
             use_patch_bias=True,
             hidden_act=hidden_act,

@@ -10,6 +10,9 @@ from jimm_amd.ops.functional import (  # noqa: F401
 )
 from jimm_amd.ops._backend import has_ext  # noqa: F401
 from jimm_amd.ops.philox_dropout import (  # noqa: F401
+    attn_dropout_scale,
+    attn_dropout_threshold,
+    attn_keep_mask,
     dropout,
     get_dropout_state,
     next_dropout_rng,
@@ -24,6 +27,9 @@ __all__ = [
     "add_cls_pos",
     "attention",
     "attention_qkv",
+    "attn_dropout_scale",
+    "attn_dropout_threshold",
+    "attn_keep_mask",
     "dropout",
     "embed_pos",
     "get_dropout_state",

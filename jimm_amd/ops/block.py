@@ -17,6 +17,10 @@ masks (ops/philox_dropout.py) in registers, fc1 saves the masked derivative,
 and the backward regenerates the fc2-site mask on dy with one elementwise
 pass. Otherwise the composite path (the reference and the CPU path) runs
 with ops.dropout. JIMM_AMD_FUSED_BLOCK=0 disables.
+
+Attention-probability dropout (p_attn > 0) needs no GEMM shape: the flash
+kernels compute its masks in registers at site ATTN_DROPOUT_SITE + site0,
+forward and backward, and no (B, H, L, L) tensor exists.
 """
 
 from __future__ import annotations
@@ -42,7 +46,11 @@ from jimm_amd.ops.hip_linear import (
     nt128_rows_k_ok,
     nt8pr_rows_ok,
 )
-from jimm_amd.ops.philox_dropout import dropout_threshold
+from jimm_amd.ops.philox_dropout import (
+    ATTN_DROPOUT_SITE,
+    attn_dropout_threshold,
+    dropout_threshold,
+)
 
 
 def _grid_widths(H: int, mlp_dim: int) -> bool:
@@ -161,6 +169,7 @@ class EncoderBlockFn(torch.autograd.Function):
         scale8, amax8,
         num_heads: int, act: str, eps: float, causal: bool, scale: float,
         p: float = 0.0, rng: torch.Tensor | None = None, site0: int = 0,
+        p_attn: float = 0.0,
     ):
         ext = _backend.ext()
         B, L, H = x.shape
@@ -178,8 +187,15 @@ class EncoderBlockFn(torch.autograd.Function):
         # both under the {seed, step} snapshot rng (fused_block_enabled has
         # checked that the bf16 HIP save-g path below takes these shapes)
         drop = dropout_threshold(p) > 0
+        # attention-probability dropout: computed inside the flash kernels
+        adrop = attn_dropout_threshold(p_attn) > 0
+        if adrop and rng is None:
+            raise RuntimeError("fused block: attention dropout needs the rng snapshot")
+        attn_drop = ("auto", p_attn, rng, ATTN_DROPOUT_SITE + site0) if adrop else ()
         if not drop:
-            p, rng = 0.0, None
+            p = 0.0
+        if not (drop or adrop):
+            rng = None
 
         # Producer-fused fp8 (BASELINE config 5): LN / bias-act kernels emit
         # the e4m3 copy of their output alongside bf16 (one extra store, no
@@ -206,6 +222,8 @@ class EncoderBlockFn(torch.autograd.Function):
         )
         if drop and (fp8 or not hip):
             raise RuntimeError("fused block: dropout runs on the bf16 HIP GEMM path only")
+        if adrop and fp8:
+            raise RuntimeError("fused block: attention dropout runs on the bf16 path only")
         # engine of the e4m3 GEMMs, per site: the in-house e4m3 kernel with
         # its epilogues fused (set_fp8(gemm="hip"), shape permitting), else
         # scaled_mm + the separate passes
@@ -224,7 +242,8 @@ class EncoderBlockFn(torch.autograd.Function):
             qkv2, _ = gemm_fwd(ext, h1.view(-1, H), wqkv, bqkv, None, None, hip=hip,
                               nt128=nt128)  # (M, 3H)
         qkv = qkv2.view(B, L, 3, num_heads, H // num_heads)
-        o, lse = ext.attn_fwd(*_split_heads(qkv), causal, scale)  # (B,nh,L,d), (B,L,nh,d) storage
+        # (B,nh,L,d), (B,L,nh,d) storage
+        o, lse = ext.attn_fwd(*_split_heads(qkv), causal, scale, *attn_drop)
         o2 = o.transpose(1, 2).reshape(-1, H)                    # free view
         a, _ = gemm_fwd(ext, o2, wproj, bproj, None, x2, hip=hip, nt128=nt128)  # + bias + residual
         a3 = a.view(B, L, H)
@@ -270,7 +289,8 @@ class EncoderBlockFn(torch.autograd.Function):
                               h1, qkv, o, lse, a, mean1, rstd1, mean2, rstd2, h2, z1, f, rng)
         ctx.dims = (B, L, H, num_heads)
         ctx.meta = (act, causal, scale)
-        ctx.drop = (p, site0)
+        ctx.drop = (p, site0, drop)
+        ctx.attn_drop = attn_drop[:2] + attn_drop[3:]  # rng comes back from saved_tensors
         ctx.hip = hip
         ctx.fp8_state = (scale8, amax8) if fp8 else None
         return y.view(B, L, H)
@@ -282,12 +302,12 @@ class EncoderBlockFn(torch.autograd.Function):
          h1, qkv, o, lse, a, mean1, rstd1, mean2, rstd2, h2, z1, f, rng) = ctx.saved_tensors
         B, L, H, nh = ctx.dims
         act, causal, scale = ctx.meta
-        p, site0 = ctx.drop
+        p, site0, drop = ctx.drop
         dy2 = dy.contiguous().view(-1, H)
         # dropout after fc2: its backward regenerates the mask on dy. dyd
         # feeds fc2's dX, dW and db; the residual branch (the LN2 addend
         # below) keeps the undropped dy.
-        dyd = ext.dropout_fwd(dy2, p, rng, site0 + 1) if rng is not None else dy2
+        dyd = ext.dropout_fwd(dy2, p, rng, site0 + 1) if drop else dy2
         h1_2 = h1.view(-1, H)
         h2_2 = h2.view(-1, H)
         hip = ctx.hip  # the forward's engine (the off-grid arm depends on M and fp8)
@@ -333,7 +353,11 @@ class EncoderBlockFn(torch.autograd.Function):
 
         # fused flash attention backward straight into the strided dqkv
         dqkv = torch.empty_like(qkv)
-        ext.attn_bwd_fused(*_split_heads(qkv), o, do_v, lse, *_split_heads(dqkv), causal, scale)
+        attn_drop = ctx.attn_drop
+        if attn_drop:
+            attn_drop = (attn_drop[0], attn_drop[1], rng, attn_drop[2])
+        ext.attn_bwd_fused(*_split_heads(qkv), o, do_v, lse, *_split_heads(dqkv), causal, scale,
+                           *attn_drop)
         dqkv2 = dqkv.view(-1, 3 * H)
 
         # QKV projection. (qkv-dX stays bf16: quantizing dqkv needs a
@@ -351,11 +375,11 @@ class EncoderBlockFn(torch.autograd.Function):
             scale8[3:4].copy_(torch.clamp(amax8[3:4] / 448.0, min=1e-12))
         return (dx, dln1w, dln1b, dwqkv, dbqkv, dwproj, dbproj, dln2w, dln2b,
                 dw1, db1, dw2, db2, None, None, None, None, None, None, None,
-                None, None, None)
+                None, None, None, None)
 
 
 def encoder_block(x, norm1, qkv, proj, norm2, fc1, fc2, *, num_heads, act, eps, causal, scale,
-                  p=0.0, rng=None, site0=0):
+                  p=0.0, rng=None, site0=0, p_attn=0.0):
     scale8 = amax8 = None
     if _FP8_STATE["enabled"] and x.is_cuda and x.dtype == torch.bfloat16:
         scale8, amax8 = _fp8_block_state(norm1, x.device)
@@ -363,5 +387,5 @@ def encoder_block(x, norm1, qkv, proj, norm2, fc1, fc2, *, num_heads, act, eps, 
         x, norm1.weight, norm1.bias, qkv.weight, qkv.bias, proj.weight, proj.bias,
         norm2.weight, norm2.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
         scale8, amax8,
-        num_heads, act, eps, causal, scale, p, rng, site0,
+        num_heads, act, eps, causal, scale, p, rng, site0, p_attn,
     )

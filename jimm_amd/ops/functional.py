@@ -23,6 +23,11 @@ import torch
 import torch.nn.functional as F
 
 from jimm_amd.ops import _backend, hip_linear
+from jimm_amd.ops.philox_dropout import (
+    attn_dropout_scale,
+    attn_dropout_threshold,
+    attn_keep_mask,
+)
 
 # ---------------------------------------------------------------------------
 # activations
@@ -109,11 +114,14 @@ def _use_fused_bwd() -> bool:
     return os.environ.get("JIMM_AMD_ATTN_BWD", "fused") == "fused"
 
 
-def _attn_bwd(ext, q, k, v, o, do, lse, dq, dk, dv, causal, scale) -> None:
+def _attn_bwd(ext, q, k, v, o, do, lse, dq, dk, dv, causal, scale, drop=None) -> None:
     """Attention backward into the caller's dq / dk / dv (strided views are
     fine: the fused kernels read and write them with no permute copies; they
-    need a unit stride in the head dimension only)."""
-    if _use_fused_bwd() and all(t.stride(3) == 1 for t in (q, k, v, o, do, dq, dk, dv)):
+    need a unit stride in the head dimension only). drop = (p, rng, site) of
+    an attention-probability dropout: fused kernels only."""
+    if drop is not None:
+        ext.attn_bwd_fused(q, k, v, o, do, lse, dq, dk, dv, causal, scale, "auto", *drop)
+    elif _use_fused_bwd() and all(t.stride(3) == 1 for t in (q, k, v, o, do, dq, dk, dv)):
         ext.attn_bwd_fused(q, k, v, o, do, lse, dq, dk, dv, causal, scale)
     else:
         for dst, src in zip((dq, dk, dv), _attn_bwd_composite(ext, q, k, v, o, do, lse, causal, scale)):
@@ -131,21 +139,27 @@ class _AttentionFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
+    def forward(ctx, q, k, v, causal, scale, p=0.0, rng=None, site=0):
         # kernel consumes strided (B,H,L,64) views directly (e.g. slices of
         # the fused qkv projection) — no permute copies on the forward path
-        o, lse = _backend.ext().attn_fwd(q, k, v, causal, scale)
-        ctx.save_for_backward(q, k, v, o, lse)
+        if rng is None:
+            o, lse = _backend.ext().attn_fwd(q, k, v, causal, scale)
+        else:  # attention-probability dropout; the backward replays rng
+            o, lse = _backend.ext().attn_fwd(q, k, v, causal, scale, "auto", p, rng, site)
+        ctx.save_for_backward(q, k, v, o, lse, rng)
         ctx.causal = causal
         ctx.scale = scale
+        ctx.drop = (p, site)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
+        q, k, v, o, lse, rng = ctx.saved_tensors
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        _attn_bwd(_backend.ext(), q, k, v, o, do, lse, dq, dk, dv, ctx.causal, ctx.scale)
-        return dq, dk, dv, None, None
+        p, site = ctx.drop
+        _attn_bwd(_backend.ext(), q, k, v, o, do, lse, dq, dk, dv, ctx.causal, ctx.scale,
+                  None if rng is None else (p, rng, site))
+        return dq, dk, dv, None, None, None, None, None
 
 
 class _AttentionQKVFn(torch.autograd.Function):
@@ -159,33 +173,62 @@ class _AttentionQKVFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, qkv, causal, scale):
-        o, lse = _backend.ext().attn_fwd(*_split_heads(qkv), causal, scale)
-        ctx.save_for_backward(qkv, o, lse)
+    def forward(ctx, qkv, causal, scale, p=0.0, rng=None, site=0):
+        if rng is None:
+            o, lse = _backend.ext().attn_fwd(*_split_heads(qkv), causal, scale)
+        else:  # attention-probability dropout; the backward replays rng
+            o, lse = _backend.ext().attn_fwd(*_split_heads(qkv), causal, scale, "auto", p, rng,
+                                             site)
+        ctx.save_for_backward(qkv, o, lse, rng)
         ctx.causal = causal
         ctx.scale = scale
+        ctx.drop = (p, site)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse = ctx.saved_tensors
+        qkv, o, lse, rng = ctx.saved_tensors
         dqkv = torch.empty_like(qkv)
+        p, site = ctx.drop
         _attn_bwd(_backend.ext(), *_split_heads(qkv), o, do, lse, *_split_heads(dqkv),
-                  ctx.causal, ctx.scale)
-        return dqkv, None, None
+                  ctx.causal, ctx.scale, None if rng is None else (p, rng, site))
+        return dqkv, None, None, None, None, None
 
 
-def attention_qkv(qkv: torch.Tensor, *, causal: bool = False, scale: float | None = None) -> torch.Tensor:
+def _attn_drop(dropout_p: float, rng: torch.Tensor | None) -> bool:
+    """True when the attention-probability dropout is active (its 8-bit
+    threshold is non-zero); then it needs the {seed, step} snapshot."""
+    if attn_dropout_threshold(dropout_p) == 0:
+        return False
+    if rng is None:
+        raise ValueError("attention dropout with p > 0 needs an rng snapshot (next_dropout_rng)")
+    return True
+
+
+def _hip_attention(x: torch.Tensor, causal: bool, drop: bool) -> bool:
+    """The flash kernels are bf16 with head_dim in {64, 72, 80, 96, 128};
+    their dropout forms are non-causal."""
+    return (_backend.use_hip(x) and x.dtype == torch.bfloat16
+            and x.shape[-1] in (64, 72, 80, 96, 128) and not (drop and causal))
+
+
+def attention_qkv(qkv: torch.Tensor, *, causal: bool = False, scale: float | None = None,
+                  dropout_p: float = 0.0, rng: torch.Tensor | None = None,
+                  site: int = 0) -> torch.Tensor:
     """qkv (B, L, 3, H, D) -> (B, H, L, D). GPU fast path for self-attention.
 
     The flash kernels are bf16 with head_dim in {64, 72, 80, 96, 128}
     (DP-padded MFMA templates); other dtypes/head dims
-    run the composite torch math (on GPU or CPU alike)."""
+    run the composite torch math (on GPU or CPU alike). dropout_p, rng and
+    site: see :func:`attention`."""
     if scale is None:
         scale = 1.0 / math.sqrt(qkv.shape[-1])
-    if _backend.use_hip(qkv) and qkv.dtype == torch.bfloat16 and qkv.shape[-1] in (64, 72, 80, 96, 128):
-        return _AttentionQKVFn.apply(qkv, causal, scale)
-    return attention(*_split_heads(qkv), causal=causal, scale=scale)
+    drop = _attn_drop(dropout_p, rng)
+    if _hip_attention(qkv, causal, drop):
+        return _AttentionQKVFn.apply(qkv, causal, scale,
+                                     *((dropout_p, rng, site) if drop else (0.0, None, 0)))
+    return attention(*_split_heads(qkv), causal=causal, scale=scale, dropout_p=dropout_p,
+                     rng=rng, site=site)
 
 
 def attention(
@@ -195,11 +238,22 @@ def attention(
     *,
     causal: bool = False,
     scale: float | None = None,
+    dropout_p: float = 0.0,
+    rng: torch.Tensor | None = None,
+    site: int = 0,
 ) -> torch.Tensor:
+    """softmax(scale q k^T) v. dropout_p > 0 drops attention probabilities:
+    O = ((P o m) s) V with the counter-based keep mask m of
+    ops/philox_dropout.py (attn_keep_mask) at ``site`` under the
+    ``{seed, step}`` snapshot ``rng``, P normalised over all keys. The flash
+    kernels compute m in registers; the composite path below (CPU, fp32 /
+    fp64, other head dims, causal with dropout) builds it with attn_keep_mask."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    if _backend.use_hip(q) and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 72, 80, 96, 128):
-        return _AttentionFn.apply(q, k, v, causal, scale)
+    drop = _attn_drop(dropout_p, rng)
+    if _hip_attention(q, causal, drop):
+        return _AttentionFn.apply(q, k, v, causal, scale,
+                                  *((dropout_p, rng, site) if drop else (0.0, None, 0)))
     # composite reference (fp32 math; float64 preserved for gradcheck)
     ref_dtype = torch.float64 if q.dtype == torch.float64 else torch.float32
     qf, kf, vf = q.to(ref_dtype), k.to(ref_dtype), v.to(ref_dtype)
@@ -209,6 +263,12 @@ def attention(
         mask = torch.ones(Lq, Lk, dtype=torch.bool, device=s.device).tril()
         s = s.masked_fill(~mask, float("-inf"))
     p = torch.softmax(s, dim=-1)
+    if drop:
+        seed, step = rng.tolist()
+        B, H, Lq, Lk = p.shape
+        keep = attn_keep_mask(B * H, Lq, Lk, dropout_p, seed, step, site, p.device)
+        p = p * (keep.view(B, H, Lq, Lk).to(ref_dtype)
+                 * attn_dropout_scale(attn_dropout_threshold(dropout_p)))
     return torch.matmul(p, vf).to(q.dtype)
 
 

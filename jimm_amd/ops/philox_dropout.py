@@ -18,6 +18,21 @@ Definition (every layer and every test agrees on it):
 * ``t = round(p * 65536)``; keep iff ``u >= t``; kept values are multiplied by
   ``s = float32(65536 / (65536 - t))``, the exact inverse of the keep rate.
 
+Attention probabilities (the flash kernels, csrc/attention*.hip) have a
+definition of their own, because a lane there owns 4 consecutive keys of one
+query (or 4 consecutive queries of one key) and would use an eighth of every
+call under the layout above:
+
+* Element ``(bh, i, j)`` = (head ``b * H + h``, query, key) takes counter
+  ``{bh, (i >> 2) | ((j >> 2) << 16), site, step & 0xffffffff}``, the same
+  key, output word ``i & 3`` and byte ``j & 3`` of that word: ``u8``. One call
+  serves a 4 x 4 block of (query, key) pairs; ``L <= 262144``.
+* ``t8 = min(round(p * 256), 255)``; keep iff ``u8 >= t8``; kept probabilities
+  are multiplied by ``s = float32(256 / (256 - t8))``. The effective rate is
+  ``t8 / 256`` (p = 0.1 runs at 26/256 = 0.1016) and ``s`` is its exact
+  inverse; ``t8 == 0`` is no dropout.
+* The attention site of an encoder block is ``ATTN_DROPOUT_SITE + site0``.
+
 The functions in this file that take plain integers are the CPU reference:
 they are the CPU path of :func:`dropout` and the oracle of the GPU tests.
 
@@ -96,6 +111,44 @@ def keep_mask(rows: int, cols: int, p: float, seed: int, step: int, site: int,
               device: torch.device | str = "cpu") -> torch.Tensor:
     """bool (rows, cols): True where the element is kept."""
     return dropout_u(rows, cols, seed, step, site, device) >= dropout_threshold(p)
+
+
+ATTN_DROPOUT_SITE = 1 << 29   # + site0 of the block; MLP sites are site0, site0 + 1
+
+
+def attn_dropout_threshold(p: float) -> int:
+    """t8 = min(round(p * 256), 255), halves up (the kernels' host code does the same)."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability must be in [0, 1), got {p}")
+    return min(int(math.floor(p * 256.0 + 0.5)), 255)
+
+
+def attn_dropout_scale(t8: int) -> float:
+    """float32(256 / (256 - t8)) as a Python float."""
+    return torch.tensor(256.0 / (256.0 - t8), dtype=torch.float32).item()
+
+
+def attn_keep_mask(BH: int, Lq: int, Lk: int, p: float, seed: int, step: int, site: int,
+                   device: torch.device | str = "cpu") -> torch.Tensor:
+    """bool (BH, Lq, Lk): True where attention probability (bh, i, j) is kept."""
+    if max(Lq, Lk) > 262144:
+        raise ValueError("attention dropout needs L <= 262144")
+    bh = torch.arange(BH, dtype=torch.int64, device=device).view(-1, 1, 1)
+    i = torch.arange(Lq, dtype=torch.int64, device=device).view(1, -1, 1)
+    j = torch.arange(Lk, dtype=torch.int64, device=device).view(1, 1, -1)
+    # one Philox call per 4 x 4 block, expanded to the elements afterwards
+    ib, jb = i[:, ::4] >> 2, j[:, :, ::4] >> 2
+    shape = (BH, ib.shape[1], jb.shape[2])
+    c2 = torch.full((), int(site) & _MASK32, dtype=torch.int64, device=device)
+    c3 = torch.full((), int(step) & _MASK32, dtype=torch.int64, device=device)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    out = philox4x32((bh.expand(shape), (ib | (jb << 16)).expand(shape), c2, c3),
+                     (seed & _MASK32, seed >> 32))
+    words = torch.stack(out, dim=-1)                                   # (BH, nib, njb, 4)
+    words = words.repeat_interleave(4, dim=1)[:, :Lq].repeat_interleave(4, dim=2)[:, :, :Lk]
+    w = torch.gather(words, 3, (i & 3).expand(BH, Lq, Lk).unsqueeze(-1)).squeeze(-1)
+    u8 = (w >> (8 * (j & 3))) & 0xFF
+    return u8 >= attn_dropout_threshold(p)
 
 
 def _dropout_ref(x: torch.Tensor, p: float, rng: torch.Tensor, site: int) -> torch.Tensor:
@@ -198,6 +251,10 @@ def next_dropout_rng(device) -> torch.Tensor:
 
 
 __all__ = [
+    "ATTN_DROPOUT_SITE",
+    "attn_dropout_scale",
+    "attn_dropout_threshold",
+    "attn_keep_mask",
     "dropout",
     "dropout_state",
     "dropout_threshold",

@@ -29,6 +29,7 @@ setup(
                 "jimm_amd/csrc/attention.hip",
                 "jimm_amd/csrc/attention_bwd.hip",
                 "jimm_amd/csrc/attention_bwd_fused.hip",
+                "jimm_amd/csrc/attention_drop.hip",
                 "jimm_amd/csrc/gemm.hip",
                 "jimm_amd/csrc/gemm8p.hip",
                 "jimm_amd/csrc/gemm8p_f8.hip",
