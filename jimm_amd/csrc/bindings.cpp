@@ -66,6 +66,12 @@ int64_t gemm_tn8p_choose_splitm(int64_t M, int64_t tiles, int64_t cus);
 torch::Tensor gemm_tn_8p(torch::Tensor dz, torch::Tensor x, int64_t splitm, bool out_bf16);
 std::vector<torch::Tensor> gemm_tn_8p_db(torch::Tensor dz, torch::Tensor x, int64_t splitm,
                                          bool out_bf16);
+bool gemm_tn8p_ragged_supported(int64_t M, int64_t N, int64_t K);
+torch::Tensor gemm_tn_8p_ragged(torch::Tensor dz, torch::Tensor x, int64_t splitm, bool out_bf16,
+                                c10::optional<torch::Tensor> out);
+std::vector<torch::Tensor> gemm_tn_8p_ragged_db(torch::Tensor dz, torch::Tensor x,
+                                                int64_t splitm, bool out_bf16,
+                                                c10::optional<torch::Tensor> out);
 bool gemm_tn_128_supported(int64_t M, int64_t N, int64_t K);
 torch::Tensor gemm_tn_128(torch::Tensor dz, torch::Tensor x, int64_t splitm, bool out_bf16);
 std::vector<torch::Tensor> gemm_tn_128_db(torch::Tensor dz, torch::Tensor x, int64_t splitm,
@@ -172,6 +178,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false);
   m.def("gemm_tn_8p_db", &gemm_tn_8p_db, "split-M TN dW with fused bias-grad colsum",
         py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false);
+  m.def("gemm_tn8p_ragged_supported", &gemm_tn8p_ragged_supported,
+        "ragged 256-tile TN dW GEMM shape check (N, K multiples of 8)");
+  m.def("gemm_tn_8p_ragged", &gemm_tn_8p_ragged,
+        "TN weight-grad GEMM, 256x256 tiles, ragged N / K, split-M; out: fp32 result tensor",
+        py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false,
+        py::arg("out") = py::none());
+  m.def("gemm_tn_8p_ragged_db", &gemm_tn_8p_ragged_db,
+        "ragged 256-tile TN dW with fused bias-grad colsum",
+        py::arg("dz"), py::arg("x"), py::arg("splitm") = 0, py::arg("out_bf16") = false,
+        py::arg("out") = py::none());
   m.def("gemm_tn_128_supported", &gemm_tn_128_supported,
         "128-tile TN dW GEMM shape check (N, K multiples of 8)");
   m.def("gemm_tn_128", &gemm_tn_128, "TN weight-grad GEMM, 128x128 tiles, ragged N / K, split-M",

@@ -72,6 +72,29 @@
 // fp32 slice of a workspace and ws_reduce_kernel folds them in fixed order
 // (deterministic), writing fp32 or bf16; grid.y == 1 stores once, straight
 // into C.
+//
+// RAGGED (gemm_tn_8p_ragged): any N % 8 == 0, Kw % 8 == 0 on
+// ceil(N/256) x ceil(Kw/256) tiles, for weight shapes off the 256 grid with
+// too many 128-tiles for gemm_tn128.hip (so400m's 4304 x 1152).  The loop, the
+// ring, the barriers and the counted waits are the ones above; the flag adds
+// no vector-memory instruction to the loop.  N and Kw are OUTPUT dimensions,
+// so an edge needs no zero fill:
+//   staging  a lane whose 8-column chunk starts at or beyond N (Kw) reads the
+//            chunk at N - 8 (Kw - 8) of the same row instead — valid and
+//            16-byte aligned — in the ring (the clamp is on the source
+//            pointers, made once) and in the register-staged tail (which
+//            keeps its zero rows).  What it brings in lands only in
+//            accumulator rows >= N / columns >= Kw.
+//   skipping a wave's 64 x 64 sub-block of row half pr that starts at or
+//            beyond N or Kw has no tr-reads and no MFMAs in phase pr; the
+//            wave still stages, waits and arrives at both barriers.  (WAR
+//            holds: a wave without reads has none to retire.)
+//   stores   the direct and the workspace store are predicated on n < N,
+//            k < Kw; the workspace is [split][N][Kw], so tn_ws_reduce applies
+//            unchanged and dW stays bitwise deterministic.
+//   fold     dealt out as above with P from the ragged k-tile count, atomics
+//            predicated on n < N.  A wave skipped for its k-columns alone
+//            still folds: it reads the one dz fragment it owns (mi = wn).
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -126,7 +149,7 @@ __device__ __forceinline__ void img_inv(int o, int& m, int& col) {
   col = nt * 16 + u * 8;
 }
 
-template <bool DBOUT, bool WSOUT>
+template <bool DBOUT, bool WSOUT, bool RAGGED = false>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
     const bf16* __restrict__ DZ, const bf16* __restrict__ X, float* __restrict__ C,
     int64_t M, int N, int Kw, int64_t chunk_m, float* __restrict__ DB) {
@@ -138,7 +161,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
   const int wave = tid / WAVE;
   const int lo = lane & 15, hi = lane >> 4;
 
-  const int nt_n = N / BN, nt_k = Kw / BKW;
+  const int nt_n = RAGGED ? (N + BN - 1) / BN : N / BN;
+  const int nt_k = RAGGED ? (Kw + BKW - 1) / BKW : Kw / BKW;
   const int wg = xcd_remap(blockIdx.x, nt_n * nt_k);
   const int n0 = (wg / nt_k) * BN;
   const int k0 = (wg % nt_k) * BKW;
@@ -151,6 +175,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
   const int nfull = (int)((m_end - m_begin) / BMS);  // full 64-row tiles
   const int nunit = 2 * nfull;                       // ring units
   const bool tail = (m_end - m_begin) % BMS != 0;
+
+  // RAGGED: live[pr] — this wave's 64 x 64 output sub-block of row half pr
+  // reaches into the matrix (wave-uniform, in scalar registers); a dead
+  // sub-block has no tr-reads and no MFMAs (header).
+  bool live[2] = {true, true};
+  if constexpr (RAGGED) {
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const bool live_k = k0 + (wv & 3) * 64 < Kw;
+    live[0] = live_k && n0 + (wv >> 2) * 64 < N;
+    live[1] = live_k && n0 + 128 + (wv >> 2) * 64 < N;
+  }
 
   f32x4_t acc[2][4][4] = {};  // [pr][mi][ni]
   // DBOUT: db[n] = sum_m dz[m][n] folded out of the A fragments already in
@@ -189,8 +224,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
   for (int j = 0; j < 2; ++j) {
     int gm, gc;
     img_inv(j * 8192 + tid * 16, gm, gc);
-    pdz[j] = DZ + (m_begin + gm) * N + n0 + gc;
-    px[j] = X + (m_begin + gm) * Kw + k0 + gc;
+    if constexpr (RAGGED) {
+      // past a ragged edge: the row's last in-range chunk (header)
+      const int cn = n0 + gc < N ? n0 + gc : N - 8;
+      const int ck = k0 + gc < Kw ? k0 + gc : Kw - 8;
+      pdz[j] = DZ + (m_begin + gm) * N + cn;
+      px[j] = X + (m_begin + gm) * Kw + ck;
+    } else {
+      pdz[j] = DZ + (m_begin + gm) * N + n0 + gc;
+      px[j] = X + (m_begin + gm) * Kw + k0 + gc;
+    }
   }
   const int ldst16 = tid * 16;
   auto issue_unit = [&](char* slot) {
@@ -218,7 +261,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
       const int m_loc = g >> 5, col = (g & 31) * 8;
       const int64_t m = mt0 + m_loc;
       s8 a = s8{}, b = s8{};
-      if (m < m_end) {
+      if constexpr (RAGGED) {
+        // columns clamped as in the ring, rows still zero-filled
+        if (m < m_end) {
+          a = *reinterpret_cast<const s8*>(DZ + m * N + (n0 + col < N ? n0 + col : N - 8));
+          b = *reinterpret_cast<const s8*>(X + m * Kw + (k0 + col < Kw ? k0 + col : Kw - 8));
+        }
+      } else if (m < m_end) {
         a = *reinterpret_cast<const s8*>(DZ + m * N + n0 + col);
         b = *reinterpret_cast<const s8*>(X + m * Kw + k0 + col);
       }
@@ -234,6 +283,33 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
   // (l>>4)*64 + (l&15) + j*16 relative to lane 0's address).
   const int lane_term = lane * 8;
 
+  // RAGGED + DBOUT: a wave whose sub-block pr is dead only because its
+  // k-columns lie beyond Kw still owns its share of the bias fold (fold_rd[pr]:
+  // its 16 fold columns start inside N).  It reads the one dz fragment it
+  // folds, mi = wn, retired by the lgkmcnt(0) of the same asm like every other
+  // read of the unit (WAR, header).
+  bool fold_rd[2] = {false, false};
+  if constexpr (RAGGED && DBOUT) {
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const int nf = n0 + (wv >> 2) * 64 + 16 * (wv & 3);
+    fold_rd[0] = !live[0] && nf < N;
+    fold_rd[1] = !live[1] && nf + 128 < N;
+  }
+  auto fold_only = [&](const char* slot, int pr) __attribute__((always_inline)) {
+    typedef const __attribute__((address_space(3))) char* lds_p;
+    const lds_p p =
+        (lds_p)(const void*)(slot + pr * 8192 + wm * 4096 + wn * 1024 + lane_term);
+    bf16x4_t l, h;
+    asm volatile(
+        "ds_read_b64_tr_b16 %0, %2 offset:0\n\t"
+        "ds_read_b64_tr_b16 %1, %2 offset:512\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(l), "=&v"(h)
+        : "v"(p)
+        : "memory");
+    db_acc[pr] += sum8(__builtin_shufflevector(l, h, 0, 1, 2, 3, 4, 5, 6, 7));
+  };
+
   // One unit = phases A (pr=0) and B (pr=1).  before_bb runs ahead of the
   // barrier of phase B, after_bb right behind it (the ring's wait / issue
   // points; empty for the tail).
@@ -248,7 +324,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
       ++unit_no;
     }
     // ---------- phase A (pr=0) ----------
-    {
+    if (RAGGED && !live[0]) {
+      // live[1] implies live[0]: no X fragments are needed either
+      if (DBOUT && do_fold && fold_rd[0]) fold_only(slot, 0);
+      raw_barrier();
+    } else {
       // B (X image) frags ni=0..3 at nt = wn*4+ni, plus A (dz) frags
       // mi=0..3 at nt = wm*4+mi (pr=0).  8+8 tr reads + lgkmcnt(0) in one
       // asm (form i).
@@ -300,7 +380,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
       __builtin_amdgcn_s_setprio(0);
     }
     // ---------- phase B (pr=1) ----------
-    {
+    if (RAGGED && !live[1]) {
+      if (DBOUT && do_fold && fold_rd[1]) fold_only(slot, 1);
+      before_bb();
+      raw_barrier();
+      after_bb();
+    } else {
       const lds_p adi = (lds_p)(const void*)(slot + 8192 + wm * 4096 + lane_term);
       bf16x4_t a0l, a0h, a1l, a1h, a2l, a2h, a3l, a3h;
       asm volatile(
@@ -378,7 +463,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
       float v_ = db_acc[pr];
       v_ += __shfl_xor(v_, 16, WAVE);
       v_ += __shfl_xor(v_, 32, WAVE);
-      if (hi == 0) atomicAdd(DB + n0 + pr * 128 + wm * 64 + 16 * wn + lo, v_);
+      if (hi == 0 && (!RAGGED || n0 + pr * 128 + wm * 64 + 16 * wn + lo < N))
+        atomicAdd(DB + n0 + pr * 128 + wm * 64 + 16 * wn + lo, v_);
     }
   }
 
@@ -398,7 +484,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_8p_kernel(
           // kernel folds the splits)
           float* dst = C + (WSOUT ? (int64_t)blockIdx.y * N * Kw : 0) +
                        (int64_t)n * Kw + k;
-          *dst = acc[pr][mi][ni][r];
+          if (!RAGGED || (n < N && k < Kw)) *dst = acc[pr][mi][ni][r];
         }
       }
 }
@@ -481,19 +567,49 @@ void tn_ws_reduce(const float* ws, void* out, int64_t n, int splits, bool out_bf
                        splits);
 }
 
+// Domain of the RAGGED instantiations: the 128-tile kernel's.
+bool gemm_tn8p_ragged_supported(int64_t M, int64_t N, int64_t K) {
+  return M >= 1 && N >= 8 && K >= 8 && N % 8 == 0 && K % 8 == 0 && N <= INT_MAX &&
+         K <= INT_MAX;
+}
+
+template <bool RAGGED>
 static torch::Tensor tn8p_run(torch::Tensor dz, torch::Tensor x, float* dbp, int64_t splitm_arg,
-                              bool out_bf16) {
+                              bool out_bf16,
+                              const c10::optional<torch::Tensor>& out = c10::nullopt) {
   // dz (M, N) bf16, x (M, Kw) bf16 -> dW (N, Kw) = dz^T @ x, fp32 or
   // (out_bf16) the fp32 result rounded once to bf16
   // (dbp != nullptr: also fold db[n] = colsum(dz) out of the A fragments)
+  // (out, RAGGED only: the fp32 (N, Kw) tensor the result is written to)
   TORCH_CHECK(dz.is_cuda() && dz.is_contiguous() && x.is_contiguous());
   TORCH_CHECK(dz.scalar_type() == torch::kBFloat16 && x.scalar_type() == torch::kBFloat16);
+  if (RAGGED) {
+    TORCH_CHECK(x.is_cuda() && dz.dim() == 2 && x.dim() == 2);
+    TORCH_CHECK(x.size(0) == dz.size(0) &&
+                    gemm_tn8p_ragged_supported(dz.size(0), dz.size(1), x.size(1)),
+                "gemm_tn_8p_ragged: needs M >= 1 and N, K multiples of 8, got M=", dz.size(0),
+                " N=", dz.size(1), " K=", x.size(1));
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(dz.data_ptr()) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+                "gemm_tn_8p_ragged: operands must be 16-byte aligned");
+  }
   const int64_t M = dz.size(0);
   const int N = dz.size(1), Kw = x.size(1);
-  TORCH_CHECK(x.size(0) == M && gemm_tn8p_supported(M, N, Kw));
+  TORCH_CHECK(x.size(0) == M && (RAGGED || gemm_tn8p_supported(M, N, Kw)));
   TORCH_CHECK(splitm_arg >= 0, "splitm must be >= 0 (0 = heuristic)");
+  if (out.has_value()) {
+    TORCH_CHECK(RAGGED && !out_bf16 && out->is_cuda() && out->is_contiguous() &&
+                    out->scalar_type() == torch::kFloat32 && out->dim() == 2 &&
+                    out->size(0) == N && out->size(1) == Kw &&
+                    reinterpret_cast<uintptr_t>(out->data_ptr()) % 16 == 0,
+                "gemm_tn_8p_ragged: out must be a contiguous 16-byte-aligned fp32 (N, K) "
+                "tensor, without out_bf16");
+  }
   auto stream = at::hip::getCurrentHIPStream();
-  const int tiles = (N / BN) * (Kw / BKW);
+  const int64_t tiles64 =
+      RAGGED ? (int64_t)((N + BN - 1) / BN) * ((Kw + BKW - 1) / BKW) : (N / BN) * (Kw / BKW);
+  TORCH_CHECK(tiles64 <= INT_MAX, "gemm_tn_8p: too many output tiles");
+  const int tiles = (int)tiles64;
   // split count: the splitm argument, else JIMM_AMD_DW_SPLITM (read once,
   // for tuning), else the round-aware choice above
   static const int splitm_env = [] {
@@ -508,6 +624,7 @@ static torch::Tensor tn8p_run(torch::Tensor dz, torch::Tensor x, float* dbp, int
   int splitm = (int)std::max<int64_t>(1, std::min<int64_t>(want, msteps));
   int64_t chunk = ((M + splitm - 1) / splitm + BMS - 1) / BMS * BMS;
   splitm = (int)((M + chunk - 1) / chunk);
+  TORCH_CHECK(!RAGGED || splitm <= 65535, "gemm_tn_8p_ragged: too many splits");
   // More than one split: each writes a private C slice of a workspace and a
   // vectorized reduce folds them in fixed order, so the whole dW is
   // deterministic (measured 662-745 -> 684-824 TF/s over an fp32 atomic
@@ -518,13 +635,14 @@ static torch::Tensor tn8p_run(torch::Tensor dz, torch::Tensor x, float* dbp, int
   torch::Tensor C, ws;
   if (use_ws) {
     ws = torch::empty({(int64_t)splitm, (int64_t)N, (int64_t)Kw}, f32);
-    C = torch::empty({(int64_t)N, (int64_t)Kw}, out_bf16 ? dz.options() : f32);
+    C = out.has_value() ? *out
+                        : torch::empty({(int64_t)N, (int64_t)Kw}, out_bf16 ? dz.options() : f32);
   } else {
-    C = torch::empty({(int64_t)N, (int64_t)Kw}, f32);
+    C = out.has_value() ? *out : torch::empty({(int64_t)N, (int64_t)Kw}, f32);
   }
   const size_t shmem = (size_t)RING * SLOT_BYTES;  // 160 KiB
 #define LAUNCH_TN(DBO, WSO)                                                                \
-  launch_lds<gemm_tn_8p_kernel<DBO, WSO>>(                                                 \
+  launch_lds<gemm_tn_8p_kernel<DBO, WSO, RAGGED>>(                                         \
       dim3(tiles, splitm), dim3(NTHREADS), shmem, shmem, stream,                           \
       reinterpret_cast<const bf16*>(dz.data_ptr()),                                        \
       reinterpret_cast<const bf16*>(x.data_ptr()),                                         \
@@ -542,13 +660,30 @@ static torch::Tensor tn8p_run(torch::Tensor dz, torch::Tensor x, float* dbp, int
 }
 
 torch::Tensor gemm_tn_8p(torch::Tensor dz, torch::Tensor x, int64_t splitm, bool out_bf16) {
-  return tn8p_run(dz, x, nullptr, splitm, out_bf16);
+  return tn8p_run<false>(dz, x, nullptr, splitm, out_bf16);
 }
 
 std::vector<torch::Tensor> gemm_tn_8p_db(torch::Tensor dz, torch::Tensor x, int64_t splitm,
                                          bool out_bf16) {
   // fused dW + bias-grad: {dW (N, Kw) fp32 or bf16, db (N) fp32}
   auto db = torch::zeros({dz.size(1)}, dz.options().dtype(torch::kFloat32));
-  auto C = tn8p_run(dz, x, db.data_ptr<float>(), splitm, out_bf16);
+  auto C = tn8p_run<false>(dz, x, db.data_ptr<float>(), splitm, out_bf16);
+  return {C, db};
+}
+
+// The same two off the 256 grid (any N % 8 == 0, Kw % 8 == 0): the RAGGED
+// instantiations. out: an fp32 (N, Kw) tensor to write dW to instead of a new
+// one (a single split stores straight into it).
+torch::Tensor gemm_tn_8p_ragged(torch::Tensor dz, torch::Tensor x, int64_t splitm, bool out_bf16,
+                                c10::optional<torch::Tensor> out) {
+  return tn8p_run<true>(dz, x, nullptr, splitm, out_bf16, out);
+}
+
+std::vector<torch::Tensor> gemm_tn_8p_ragged_db(torch::Tensor dz, torch::Tensor x,
+                                                int64_t splitm, bool out_bf16,
+                                                c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(dz.is_cuda() && dz.dim() == 2);
+  auto db = torch::zeros({dz.size(1)}, dz.options().dtype(torch::kFloat32));
+  auto C = tn8p_run<true>(dz, x, db.data_ptr<float>(), splitm, out_bf16, out);
   return {C, db};
 }

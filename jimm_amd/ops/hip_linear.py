@@ -22,7 +22,13 @@ Two engines run a GEMM:
     where N % 256 == 0 and K % 256 == 0, else the 128-tile kernel of
     csrc/gemm_tn128.hip for any N % 8 == 0, K % 8 == 0 with M >= 256 and at
     most 162 output tiles of 128 x 128, 243 with the bias fold (ViT-S,
-    so400m's proj and qkv, class heads); every other dW goes to torch.matmul;
+    so400m's proj and qkv, class heads); beyond those caps the ragged form
+    of the 256-tile kernel (gemm_tn_8p_ragged) with M >= 16384 where N x K
+    fills 89% of its 256 x 256 tiles and N 98% of its tile rows (``_tn8pr_ok``:
+    so400m's fc1; fc2 and qkv without a bias gradient measured level with
+    rocBLAS and stay there, profiles/dw_ragged_NOTES.md; JIMM_AMD_DW_RAGGED=1
+    sends every off-grid dW to it, 0 none); every other dW goes to
+    torch.matmul;
   * hipBLASLt/rocBLAS through torch (with the committed MI355X TunableOp
     table) + the separate fused bias+act(+residual) elementwise kernel.
 
@@ -341,6 +347,56 @@ def _tn128_ok(ext, dz, x2, fold: bool) -> bool:
     )
 
 
+def _dw_ragged_mode() -> str:
+    # JIMM_AMD_DW_RAGGED: "1" sends every off-grid dW in the domain of the
+    # ragged 256-tile TN kernel to it, "0" none; unset: the measured rule of
+    # _tn8pr_ok.
+    return os.environ.get("JIMM_AMD_DW_RAGGED", "")
+
+
+# The ragged 256-tile TN kernel (gemm_tn_8p_ragged, csrc/gemm_tn8p.hip) by
+# default, among the shapes beyond the 128-tile kernel's tile caps (which ran
+# torch.matmul so far): the fewest rows, the least share of its
+# ceil(N/256) x ceil(K/256) output tiles that N x K must fill, and the least
+# share of its ceil(N/256) tile rows that N must. Of so400m's sites beyond the
+# caps, fc1 (4304 x 1152: 89% of 85 tiles, N 98.9%) took 5-14% less time
+# than rocBLAS (dW + db: 4-18% less than rocBLAS + colsum) at M = 46656 and
+# 65536 and about half its time at 16384, beyond the spread in both runs;
+# fc2 (1152 x 4304: the same 89%, N 90%) was level or behind with db at
+# 46656, and qkv without db (3456 x 1152, 87%) behind at 16384 and level at
+# 65536 in one run: both stay on rocBLAS.
+# benchmarks/dw_ragged_bench.py; profiles/dw_ragged_NOTES.md.
+_TN8PR_MIN_M = 16384
+_TN8PR_MIN_FILL = 0.89
+_TN8PR_MIN_FILL_N = 0.98
+
+
+def _tn8pr_ok(ext, dz, x2, fold: bool, forced: bool) -> bool:
+    """Whether an off-grid dW runs the ragged 256-tile TN kernel: its domain
+    (N and K multiples of 8, contiguous 16-byte-aligned bf16 operands), nothing
+    under set_fp8(True), and either JIMM_AMD_DW_RAGGED=1 (forced) or the
+    measured rule: what the 128-tile kernel's row floor admits and its tile
+    caps decline, at or above the row floor and the fill above. fold: the call
+    will use the bias fold."""
+    M, N, K = dz.shape[0], dz.shape[1], x2.shape[1]
+    if not (
+        not _FP8_STATE["enabled"]
+        and ext.gemm_tn8p_ragged_supported(M, N, K)
+        and x2.dtype == torch.bfloat16
+        and dz.is_contiguous()
+        and x2.is_contiguous()
+        and dz.data_ptr() % 16 == 0
+        and x2.data_ptr() % 16 == 0
+    ):
+        return False
+    return forced or (
+        M >= max(_TN128_MIN_M, _TN8PR_MIN_M)
+        and -(-N // 128) * -(-K // 128) > (_TN128_MAX_TILES_DB if fold else _TN128_MAX_TILES)
+        and N * K >= _TN8PR_MIN_FILL * 65536 * -(-N // 256) * -(-K // 256)
+        and N >= _TN8PR_MIN_FILL_N * 256 * -(-N // 256)
+    )
+
+
 def gemm_dw_db(ext, dz, x2, out_dtype, need_dw: bool = True, need_db: bool = True):
     """(dW = dz^T @ x2 | None, db = colsum(dz) | None). The in-house split-M
     TN kernels (fp32 accumulate, deterministic fixed-order combine of the
@@ -349,14 +405,21 @@ def gemm_dw_db(ext, dz, x2, out_dtype, need_dw: bool = True, need_db: bool = Tru
     of a separate full re-read of dz. That fold adds fp32 atomically, so
     deterministic mode does not take it. Shapes on the 256 grid run the
     256-tile kernel; any other N % 8 == 0, K % 8 == 0 shape with M >= 256 and
-    few enough output tiles the 128-tile kernel; the rest torch.matmul +
-    colsum."""
+    few enough output tiles the 128-tile kernel; of what that leaves, the
+    ragged 256-tile kernel what its measured rule admits (_tn8pr_ok); the rest
+    torch.matmul + colsum. JIMM_AMD_DW_RAGGED=1 puts the ragged kernel ahead
+    of the 128-tile one, for every shape of its domain; 0 turns it off."""
     tn = need_dw and _gemm_mode() == "hip" and dz.dtype == torch.bfloat16
     fold = need_db and not _deterministic()
+    ragged = _dw_ragged_mode()
     if tn and ext.gemm_tn8p_supported(dz.shape[0], dz.shape[1], x2.shape[1]):
         tn_dw, tn_dw_db = ext.gemm_tn_8p, ext.gemm_tn_8p_db
+    elif tn and ragged == "1" and _tn8pr_ok(ext, dz, x2, fold, True):
+        tn_dw, tn_dw_db = ext.gemm_tn_8p_ragged, ext.gemm_tn_8p_ragged_db
     elif tn and _tn128_ok(ext, dz, x2, fold):
         tn_dw, tn_dw_db = ext.gemm_tn_128, ext.gemm_tn_128_db
+    elif tn and ragged != "0" and _tn8pr_ok(ext, dz, x2, fold, False):
+        tn_dw, tn_dw_db = ext.gemm_tn_8p_ragged, ext.gemm_tn_8p_ragged_db
     else:
         tn = False
     if tn and fold:
