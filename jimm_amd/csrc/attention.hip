@@ -20,6 +20,8 @@
 // workgroup: attn_fwd_small_kernel (Lq == Lk <= 80) and
 // attn_fwd_resident_kernel (81 <= Lq == Lk <= 256, non-causal, ViT-B L=197);
 // both D = 64, see their header comments and the dispatch in attn_fwd.
+// attn_fwd_resident80_kernel is the resident kernel for D = 72 and 80
+// (so400m L = 256, ViT-H), with 80-column images of its own.
 //
 // Attention-probability dropout (template flag DROP of the tiled and the
 // resident kernel; the mask definition and the lane-sharing of its Philox
@@ -678,6 +680,194 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_resident_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Resident forward for head dims 72 and 80 (so400m, ViT-H; same L domain,
+// non-causal, no dropout form). Work split, softmax and synchronisation are
+// those of attn_fwd_resident_kernel above; what the head dim changes:
+//   Images. K and V are noff80 images (mfma.h): 32-row blocks of FIVE 16-d
+//     sub-blocks, rows 32 B apart inside a sub-block, 160 B of image per key.
+//     Columns Dr..79 are written as zeros at D = 72 (never left stale: LDS
+//     garbage can hold NaN bits, and NaN * 0 = NaN). The image is
+//     sub-block-major, not row-major with a 160-byte pitch, so the bank
+//     picture of the D = 64 image carries over unchanged: a ds_read_b128
+//     fragment read puts lane (lo, hi) at sub-block 2s + (hi >> 1), byte
+//     32 lo + 16 (hi & 1), i.e. each 16-lane quarter touches 16 different
+//     32-byte rows of one 1 KiB sub-block exactly as at D = 64, and the
+//     sub-blocks are 1 KiB apart (the same banks). No swizzle and no pitch
+//     padding: either would have to be undone in the tr reads. Each
+//     ds_read_b64_tr_b16 reads 512 contiguous bytes (base + lane * 8), which
+//     is conflict-free, and so is the tail's ds_read_b64 below.
+//     LDS is the two images and nothing else: 71 680 B at L = 197 and
+//     81 920 B at L = 256 (half of the 160 KiB exactly), two workgroups per
+//     CU over the whole domain.
+//   The 80-deep d contraction is three v_mfma_f32_16x16x32_bf16 steps, the
+//     third 16 deep: lanes hi < 2 hold d = 64 + 8 hi .. + 8 of row lo and
+//     lanes hi >= 2 hold zeros made in registers; they read nothing, so no
+//     read runs past column 79 into another row. The 32 reading lanes cover
+//     16 rows x 32 B of sub-block 4, 512 contiguous bytes. The Q tail comes
+//     from global and is zero in registers where 64 + 8 hi >= Dr (what
+//     follows a head's 72 columns in a fused QKV row is the next head).
+//     (A 16-deep v_mfma_f32_16x16x16_bf16 on a 4-per-lane fragment was built
+//     first and returned wrong scores on hardware: issued straight after the
+//     two 32-deep steps with their result as its C operand, it read
+//     accumulator registers 0 and 1 before they were written. One MFMA shape
+//     throughout has no such dependency between shapes.)
+//   The d output side has five tiles: tr_frag_x4 plus tr_frag_5th, the fifth
+//     tile's MFMA issued under its own two tr reads so that at most four
+//     fragments are live. A lane ends with d = 16 dt + 4 hi .. + 4 of query
+//     lo; the fifth tile's 8-byte store is dropped where 64 + 4 hi >= Dr.
+//   Registers: the 2 * NBLK score tiles (64 at NBLK = 8), five accumulator
+//     tiles (20), ONE strip's Q fragments (12; the second strip's rows are
+//     loaded when its turn comes, not held from the start), four V fragments
+//     (16), P (4). No scratch: docs/kernels.md has the compiler's table.
+// ---------------------------------------------------------------------------
+
+template <int NBLK>
+__global__ __launch_bounds__(512, 4) void attn_fwd_resident80_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
+    bf16* __restrict__ o, float* __restrict__ lse, int L, int Dr, float scale, int H,
+    hstride q_s, hstride k_s, hstride v_s, hstride o_s) {
+  constexpr int DI = RES80_D;
+  constexpr int LP = 32 * NBLK;  // image rows: whole 32-row blocks
+  constexpr int IMG = LP * DI;
+  constexpr int NTHR = 64 * NBLK;  // the image has exactly 5 16-B chunks per thread
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  short* imgK = reinterpret_cast<short*>(smem);
+  short* imgV = imgK + IMG;
+
+  const int tid = threadIdx.x;
+  const int wave = tid / WAVE;
+  const int lane = tid % WAVE;
+  const int lo = lane & 15, hi = lane >> 4;
+  const int64_t bh = blockIdx.x;
+  const bf16* qp = head_ptr(q, q_s, bh, H);
+  const bf16* kp = head_ptr(k, k_s, bh, H);
+  const bf16* vp = head_ptr(v, v_s, bh, H);
+  const bool tail_ok = 64 + 4 * hi < Dr;  // output side: this lane's 4 tail columns exist
+
+  // ---- a strip's Q rows: B-fragments of the three steps, [2] the 16-deep tail --
+  bf16x8 qb[3];
+  auto load_q = [&](int s0) {
+    const bf16* row = qp + (int64_t)min(s0 + lo, L - 1) * q_s.l;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) qb[s] = *reinterpret_cast<const bf16x8*>(row + 32 * s + hi * 8);
+    qb[2] = bf16x8{};
+    if (hi < 2 && 64 + 8 * hi < Dr) qb[2] = *reinterpret_cast<const bf16x8*>(row + 64 + 8 * hi);
+  };
+  load_q(16 * wave);  // in flight under the staging
+
+  // ---- stage K, V ------------------------------------------------------------
+#pragma unroll
+  for (int it = 0; it < 5; ++it) {
+    const int idx = tid + it * NTHR;
+    const int row = idx / 10, d8 = (idx % 10) * 8;
+    const int rc = min(row, L - 1);
+    bf16x8 kk{}, vv{};
+    if (row < L && d8 < Dr) {
+      kk = *reinterpret_cast<const bf16x8*>(kp + (int64_t)rc * k_s.l + d8);
+      vv = *reinterpret_cast<const bf16x8*>(vp + (int64_t)rc * v_s.l + d8);
+    }
+    const int off = noff80(row, d8);
+    *reinterpret_cast<bf16x8*>(imgK + off) = kk;
+    *reinterpret_cast<bf16x8*>(imgV + off) = vv;
+  }
+  __syncthreads();
+
+  const float c = scale * 1.44269504088896340736f;  // scores in log2 units
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int s0 = 16 * (wave + i * NBLK);
+    if (s0 >= L) continue;  // wave-uniform
+    if (i == 1) load_q(s0);
+    const bool sok = s0 + lo < L;
+
+    // ---- S^T = K . Q^T, all 2*NBLK key tiles, 32 + 32 + 16 deep --------------
+    f32x4 sc[NBLK][2];
+#pragma unroll
+    for (int kb = 0; kb < NBLK; ++kb) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        sc[kb][t] = f32x4{};
+        // whole 16-key tile is padding (wave-uniform; masked below)
+        if (kb == NBLK - 1 && 32 * kb + 16 * t >= L) continue;
+        const int krow = 32 * kb + 16 * t + lo;
+        bf16x8 ka[3];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+          ka[s] = *reinterpret_cast<const bf16x8*>(imgK + noff80(krow, 32 * s + hi * 8));
+        ka[2] = bf16x8{};
+        if (hi < 2) ka[2] = *reinterpret_cast<const bf16x8*>(imgK + noff80(krow, 64 + 8 * hi));
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) sc[kb][t] = MFMA16(ka[s], qb[s], sc[kb][t]);
+        __builtin_amdgcn_s_setprio(0);
+      }
+    }
+
+    // ---- row max over every key (query = lane lo) ----------------------------
+    float m = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < NBLK; ++kb) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float x = sc[kb][t][r] * c;
+          if (kb == NBLK - 1 && 32 * kb + 16 * t + 4 * hi + r >= L) x = -INFINITY;
+          sc[kb][t][r] = x;
+          m = fmaxf(m, x);
+        }
+      }
+    }
+    m = fmaxf(m, __shfl_xor(m, 16, WAVE));
+    m = fmaxf(m, __shfl_xor(m, 32, WAVE));
+    const float msub = sok ? m : INFINITY;  // padded query rows: P = exp2(-inf) = 0
+
+    // ---- P = exp2(S - m) 32 keys at a time; O^T += V^T . P^T, five d-tiles ----
+    float lsum = 0.f;
+    f32x4 acc[5] = {};
+#pragma unroll
+    for (int kb = 0; kb < NBLK; ++kb) {
+      bf16x8 pf;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = __builtin_amdgcn_exp2f(sc[kb][t][r] - msub);
+          lsum += p;
+          pf[4 * t + r] = f2bfs(p);
+        }
+      }
+      const lds_cp vbase = (lds_cp)(const void*)(imgV + kb * 32 * DI) + lane * 8;
+      bf16x8 vfr[4];
+      tr_frag_x4(vbase, vfr);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) acc[dt] = MFMA16(vfr[dt], pf, acc[dt]);
+      __builtin_amdgcn_s_setprio(0);
+      acc[4] = MFMA16(tr_frag_5th(vbase), pf, acc[4]);
+    }
+    lsum += __shfl_xor(lsum, 16, WAVE);
+    lsum += __shfl_xor(lsum, 32, WAVE);
+
+    // acc holds O^T tiles: lane = query lo, d = 16dt + 4hi + r -> 8-byte stores
+    if (sok) {
+      const float invl = 1.f / lsum;
+      bf16* op = head_ptr(o, o_s, bh, H) + (int64_t)(s0 + lo) * o_s.l + 4 * hi;
+#pragma unroll
+      for (int dt = 0; dt < 5; ++dt) {
+        if (dt == 4 && !tail_ok) continue;  // d >= Dr: the next head's columns
+        bf16x4 pk;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pk[r] = f2bfs(acc[dt][r] * invl);
+        *reinterpret_cast<bf16x4*>(op + 16 * dt) = pk;
+      }
+      if (hi == 0)
+        lse[bh * L + s0 + lo] = __builtin_fmaf(m, 0.69314718055994530942f, __logf(lsum));
+    }
+  }
+}
+
 }  // namespace
 
 // Launch of the DROP instantiations (non-causal; resident inside the resident
@@ -738,12 +928,15 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
   const unsigned t8 = attn_drop_threshold(p);
   check_attn_drop("attn_fwd", t8, causal, Lq, Lk);
   const bool aligned = res_aligned({&q, &k, &v});  // o is allocated below, aligned
-  const bool resident_ok = Dr == 64 && Lq == Lk && !causal && Lk >= RES_LMIN &&
+  // D = 72 and 80 have resident kernels of their own, without a dropout form
+  const bool res80 = (Dr == 72 || Dr == 80) && t8 == 0;
+  const bool resident_ok = (Dr == 64 || res80) && Lq == Lk && !causal && Lk >= RES_LMIN &&
                            Lk <= RES_LMAX && aligned;
   TORCH_CHECK(path != "resident" || resident_ok,
-              "attn_fwd: path=resident needs D == 64, Lq == Lk, non-causal, ", RES_LMIN,
-              " <= L <= ", RES_LMAX, " and 16-byte aligned rows; got D=", Dr, " Lq=", Lq,
-              " Lk=", Lk, " causal=", causal, " aligned=", aligned);
+              "attn_fwd: path=resident needs D in {64, 72, 80} (no dropout at 72 and 80), "
+              "Lq == Lk, non-causal, ", RES_LMIN, " <= L <= ", RES_LMAX,
+              " and 16-byte aligned rows; got D=", Dr, " Lq=", Lq, " Lk=", Lk,
+              " causal=", causal, " aligned=", aligned, " p=", p);
   // O written in (B,L,H,D) memory order so the model's (B,L,H*D) reshape is
   // a free view (no permute copy)
   auto o = torch::empty({B, Lq, H, Dr}, q.options()).permute({0, 2, 1, 3});
@@ -751,11 +944,26 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
   const unsigned BH = (unsigned)((int64_t)B * H);
   auto stream = at::hip::getCurrentHIPStream();
   if (t8 > 0) {
-    attn_fwd_drop(q, k, v, o, lse, scale, path != "tiled" && resident_ok,
+    attn_fwd_drop(q, k, v, o, lse, scale, path != "tiled" && resident_ok && Dr == 64,
                   make_attn_drop_args(t8, rng, site, q));
     return {o, lse};
   }
-  if (path != "tiled" && resident_ok) {
+  // D = 72 / 80: auto takes the resident kernel over its whole domain, as at
+  // D = 64 (1.47-2.10x ahead of the tiled kernel at every measured (D, L):
+  // profiles/attn_resident_d80_NOTES.md)
+  if (path != "tiled" && resident_ok && res80) {
+    const int nblk = (Lk + 31) / 32;
+    const size_t rshmem = (size_t)2 * nblk * 32 * RES80_D * sizeof(short);
+    constexpr size_t rshmem_max = (size_t)2 * RES_LMAX * RES80_D * sizeof(short);
+    with_int<3, 4, 5, 6, 7, 8>(nblk, "resident block count", [&](auto nb) {
+      launch_lds<attn_fwd_resident80_kernel<decltype(nb)::value>>(
+          dim3(BH), dim3(nblk * WAVE), rshmem, rshmem_max, stream, bf16_ptr(q), bf16_ptr(k),
+          bf16_ptr(v), bf16_ptr(o), lse.data_ptr<float>(), Lk, Dr, (float)scale, H, hstrides(q),
+          hstrides(k), hstrides(v), hstrides(o));
+    });
+    return {o, lse};
+  }
+  if (path != "tiled" && resident_ok && Dr == 64) {
     // one wave per 32 rows (two 16-row strips each); K and V images only.
     // The LDS limit is raised once, to the largest supported L.
     const int nblk = (Lk + 31) / 32;

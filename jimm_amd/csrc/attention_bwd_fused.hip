@@ -18,6 +18,8 @@
 //   attn_bwd_small_kernel    — Lq == Lk <= 80
 //   attn_bwd_resident_kernel — 81 <= Lq == Lk <= 256, non-causal (ViT-B L=197)
 // (both D = 64; see their header comments and the dispatch in attn_bwd_fused).
+//   attn_bwd_resident80_kernel — the resident kernel for D = 72 and 80, same
+//     L domain, 80-column images of its own.
 //
 // Attention-probability dropout (template flag DROP of the tiled pair and the
 // resident kernel; mask and call sharing in common.h, attn_drop_u). With keep
@@ -1114,6 +1116,295 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_resident_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Resident fused backward for head dims 72 and 80 (same L domain, non-causal,
+// no dropout form). Phases, barriers and the accumulator-to-fragment trick are
+// those of attn_bwd_resident_kernel above; what the head dim changes:
+//   Images are noff80 (mfma.h; bank argument in attention.hip,
+//     attn_fwd_resident80_kernel): five 16-d sub-blocks, 160 B per row,
+//     columns Dr..79 written as zeros at D = 72, for Q and dO as for K and V.
+//     LDS = two images + lse + delta = 328 B per image row: 73 472 B at
+//     L = 197 and 83 968 B at L = 256. By LDS two workgroups share a CU up to
+//     L = 224 (LP = 224); at 225 <= L <= 256 the lse / delta vectors push one
+//     workgroup past half of the 160 KiB and a CU holds one (8 waves). By
+//     registers (136 VGPRs, 3 waves per SIMD, 12 per CU) two workgroups fit
+//     up to L = 192 (6 waves each); from L = 193 a CU holds one workgroup.
+//   Both 80-deep contractions (S and dP, in either phase) are three MFMA16
+//     steps, the third 16 deep: lanes hi < 2 hold d = 64 + 8 hi .. + 8, lanes
+//     hi >= 2 zeros made in registers (they read nothing, so no read runs
+//     past column 79). Register-side tail fragments are zero where
+//     64 + 8 hi >= Dr. delta sweeps the same three fragments of dO and O, so
+//     it covers exactly the head's Dr columns.
+//   dQ^T, dK^T and dV^T have five tiles: tr_frag_x4 + tr_frag_5th, at most
+//     four fragments live; the fifth tile's 8-byte stores are dropped where
+//     64 + 4 hi >= Dr.
+//   Registers. Two strips per wave as at D = 64, but phase 2 does not hold
+//     both key strips' K / V rows from before the images are overwritten
+//     (2 x 24 VGPRs): each strip loads its own 16 rows from global (L2-hot)
+//     when its turn comes, and the image fragments of S and of dP are read
+//     one operand after the other. At the 128 VGPRs of four waves per SIMD
+//     the kernel still spilled (20 to 40 B per lane), so it is bounded at
+//     three waves per SIMD: 136 VGPRs, no scratch (table in docs/kernels.md).
+// ---------------------------------------------------------------------------
+
+#ifndef JIMM_ATTN_DROP_TU  // not a template: keep it out of the dropout unit
+__global__ __launch_bounds__(512, 3) void attn_bwd_resident80_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
+    const bf16* __restrict__ o, const bf16* __restrict__ dO, const float* __restrict__ lse,
+    bf16* __restrict__ dq, bf16* __restrict__ dk, bf16* __restrict__ dv, int L, int Dr,
+    float scale, int H, hstride q_s, hstride k_s, hstride v_s, hstride o_s, hstride do_s,
+    hstride dq_s, hstride dk_s, hstride dv_s) {
+  constexpr int DI = RES80_D;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int LP = (L + 31) & ~31;  // image rows: whole 32-row blocks
+  const int IMG = LP * DI;
+  short* imgA = reinterpret_cast<short*>(smem);  // K, then Q
+  short* imgB = imgA + IMG;                      // V, then dO
+  float* lse_s = reinterpret_cast<float*>(imgB + IMG);  // [LP]
+  float* dl_s = lse_s + LP;                             // [LP] delta
+
+  const int tid = threadIdx.x;
+  const int nthr = blockDim.x;  // 64 * LP/32: the image has exactly 5 16-B chunks per thread
+  const int nw = nthr / WAVE;
+  const int wave = tid / WAVE;
+  const int lane = tid % WAVE;
+  const int lo = lane & 15, hi = lane >> 4;
+  const int64_t bh = blockIdx.x;
+  const bf16* qp = head_ptr(q, q_s, bh, H);
+  const bf16* kp = head_ptr(k, k_s, bh, H);
+  const bf16* vp = head_ptr(v, v_s, bh, H);
+  const bf16* op = head_ptr(o, o_s, bh, H);
+  const bf16* dop = head_ptr(dO, do_s, bh, H);
+  const int nblk = LP / 32;
+  const bool tail_ok = 64 + 4 * hi < Dr;  // this lane's 4 tail columns exist
+
+  // one row's register fragments of the three steps, [2] the 16-deep tail
+  const bool tail_ld = hi < 2 && 64 + 8 * hi < Dr;
+  auto load_frags = [&](const bf16* row, bf16x8 (&f)[3]) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) f[s] = *reinterpret_cast<const bf16x8*>(row + 32 * s + hi * 8);
+    f[2] = bf16x8{};
+    if (tail_ld) f[2] = *reinterpret_cast<const bf16x8*>(row + 64 + 8 * hi);
+  };
+  // the same three fragments of image row `row`
+  auto img_frags = [&](const short* img, int row, bf16x8 (&f)[3]) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      f[s] = *reinterpret_cast<const bf16x8*>(img + noff80(row, 32 * s + hi * 8));
+    f[2] = bf16x8{};
+    if (hi < 2) f[2] = *reinterpret_cast<const bf16x8*>(img + noff80(row, 64 + 8 * hi));
+  };
+
+  // ---- a strip's own Q/dO rows (phase-1 B-fragments) and its delta ---------
+  bf16x8 qb[3], dob[3];
+  float dl;
+  auto load_rows = [&](int s0) {
+    const int srow = min(s0 + lo, L - 1);
+    bf16x8 ov[3];
+    load_frags(qp + (int64_t)srow * q_s.l, qb);
+    load_frags(dop + (int64_t)srow * do_s.l, dob);
+    load_frags(op + (int64_t)srow * o_s.l, ov);
+    dl = 0.f;
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dl += bfs2f(dob[s][j]) * bfs2f(ov[s][j]);
+    dl += __shfl_xor(dl, 16, WAVE);
+    dl += __shfl_xor(dl, 32, WAVE);  // delta[s0 + lo] = rowsum(dO o O)
+  };
+  load_rows(16 * wave);  // first strip
+
+  // ---- stage K, V + lse ----------------------------------------------------
+#pragma unroll
+  for (int it = 0; it < 5; ++it) {
+    const int idx = tid + it * nthr;
+    const int row = idx / 10, d8 = (idx % 10) * 8;
+    const int rc = min(row, L - 1);
+    bf16x8 kk{}, vv{};
+    if (row < L && d8 < Dr) {
+      kk = *reinterpret_cast<const bf16x8*>(kp + (int64_t)rc * k_s.l + d8);
+      vv = *reinterpret_cast<const bf16x8*>(vp + (int64_t)rc * v_s.l + d8);
+    }
+    const int off = noff80(row, d8);
+    *reinterpret_cast<bf16x8*>(imgA + off) = kk;
+    *reinterpret_cast<bf16x8*>(imgB + off) = vv;
+  }
+  for (int i = tid; i < LP; i += nthr) {
+    lse_s[i] = i < L ? lse[bh * L + i] : 0.f;
+    dl_s[i] = 0.f;
+  }
+  __syncthreads();  // barrier 1
+
+  // ---- phase 1: wave = query strips wave, wave + nw -----------------------
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int s0 = 16 * (wave + i * nw);
+    if (s0 >= L) continue;  // wave-uniform
+    if (i == 1) load_rows(s0);
+    const bool sok = s0 + lo < L;
+    const float lse_q = lse_s[min(s0 + lo, L - 1)];
+    const float dli = dl;
+    if (hi == 0) dl_s[s0 + lo] = dli;
+    f32x4 adq[5] = {};
+    for (int kb = 0; kb < nblk; ++kb) {
+      f32x4 sc[2] = {}, dpc[2] = {};
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if (32 * kb + 16 * t >= L) continue;  // whole 16-key tile is padding (wave-uniform)
+        bf16x8 fa[3];  // one operand's fragments at a time (register budget)
+        img_frags(imgA, 32 * kb + 16 * t + lo, fa);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) sc[t] = MFMA16(fa[s], qb[s], sc[t]);
+        __builtin_amdgcn_s_setprio(0);
+        img_frags(imgB, 32 * kb + 16 * t + lo, fa);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) dpc[t] = MFMA16(fa[s], dob[s], dpc[t]);
+        __builtin_amdgcn_s_setprio(0);
+      }
+      bf16x8 dsa;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = 32 * kb + 16 * t + 4 * hi + r;
+          const bool ok = sok && key < L;
+          const float p = ok ? __expf(sc[t][r] * scale - lse_q) : 0.f;
+          const float ds = ok ? p * (dpc[t][r] - dli) * scale : 0.f;
+          dsa[4 * t + r] = f2bfs(ds);
+        }
+      }
+      const lds_cp kbase = (lds_cp)(const void*)(imgA + kb * 32 * DI) + lane * 8;
+      bf16x8 bfr[4];
+      tr_frag_x4(kbase, bfr);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) adq[dt] = MFMA16(bfr[dt], dsa, adq[dt]);
+      __builtin_amdgcn_s_setprio(0);
+      adq[4] = MFMA16(tr_frag_5th(kbase), dsa, adq[4]);
+    }
+    // adq holds dQ^T tiles: lane = query lo, d = 16dt + 4hi + r -> 8-byte stores
+    if (sok) {
+      bf16* dqp = head_ptr(dq, dq_s, bh, H) + (int64_t)(s0 + lo) * dq_s.l + 4 * hi;
+#pragma unroll
+      for (int dt = 0; dt < 5; ++dt) {
+        if (dt == 4 && !tail_ok) continue;  // d >= Dr: the next head's columns
+        bf16x4 pk;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pk[r] = f2bfs(adq[dt][r]);
+        *reinterpret_cast<bf16x4*>(dqp + 16 * dt) = pk;
+      }
+    }
+  }
+
+  // ---- between the phases: Q/dO replace K/V in the two image slots --------
+  bf16x8 qst[5], dst[5];
+#pragma unroll
+  for (int it = 0; it < 5; ++it) {
+    const int idx = tid + it * nthr;
+    const int row = idx / 10, d8 = (idx % 10) * 8;
+    const int rc = min(row, L - 1);
+    qst[it] = dst[it] = bf16x8{};
+    if (row < L && d8 < Dr) {
+      qst[it] = *reinterpret_cast<const bf16x8*>(qp + (int64_t)rc * q_s.l + d8);
+      dst[it] = *reinterpret_cast<const bf16x8*>(dop + (int64_t)rc * do_s.l + d8);
+    }
+  }
+  __syncthreads();  // barrier 2: K/V images retired, every strip's delta in LDS
+#pragma unroll
+  for (int it = 0; it < 5; ++it) {
+    const int idx = tid + it * nthr;
+    const int off = noff80(idx / 10, (idx % 10) * 8);
+    *reinterpret_cast<bf16x8*>(imgA + off) = qst[it];
+    *reinterpret_cast<bf16x8*>(imgB + off) = dst[it];
+  }
+  __syncthreads();  // barrier 3: Q/dO images published
+
+  // ---- phase 2: wave = key strips wave, wave + nw --------------------------
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int s0 = 16 * (wave + i * nw);
+    if (s0 >= L) continue;  // wave-uniform
+    const bool sok = s0 + lo < L;
+    // the strip's own K/V rows as B-fragments, from global (a clamped row's
+    // P and dS are forced to 0 below)
+    bf16x8 kbf[3], vbf[3];
+    {
+      const int srow = min(s0 + lo, L - 1);
+      load_frags(kp + (int64_t)srow * k_s.l, kbf);
+      load_frags(vp + (int64_t)srow * v_s.l, vbf);
+    }
+    f32x4 adk[5] = {}, adv[5] = {};
+    for (int qblk = 0; qblk < nblk; ++qblk) {
+      f32x4 sc[2] = {}, dpc[2] = {};
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if (32 * qblk + 16 * t >= L) continue;  // whole 16-query tile is padding
+        bf16x8 fa[3];  // one operand's fragments at a time (register budget)
+        img_frags(imgA, 32 * qblk + 16 * t + lo, fa);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) sc[t] = MFMA16(fa[s], kbf[s], sc[t]);
+        __builtin_amdgcn_s_setprio(0);
+        img_frags(imgB, 32 * qblk + 16 * t + lo, fa);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) dpc[t] = MFMA16(fa[s], vbf[s], dpc[t]);
+        __builtin_amdgcn_s_setprio(0);
+      }
+      bf16x8 pa, dsa;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int qi0 = 32 * qblk + 16 * t + 4 * hi;
+        const f32x4 ls4 = *reinterpret_cast<const f32x4*>(lse_s + qi0);
+        const f32x4 dl4 = *reinterpret_cast<const f32x4*>(dl_s + qi0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool ok = sok && qi0 + r < L;
+          const float p = ok ? __expf(sc[t][r] * scale - ls4[r]) : 0.f;
+          const float ds = ok ? p * (dpc[t][r] - dl4[r]) * scale : 0.f;
+          pa[4 * t + r] = f2bfs(p);
+          dsa[4 * t + r] = f2bfs(ds);
+        }
+      }
+      const lds_cp dbase = (lds_cp)(const void*)(imgB + qblk * 32 * DI) + lane * 8;
+      const lds_cp qbase = (lds_cp)(const void*)(imgA + qblk * 32 * DI) + lane * 8;
+      bf16x8 bfr[4];  // one fragment set at a time (register budget)
+      tr_frag_x4(dbase, bfr);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) adv[dt] = MFMA16(bfr[dt], pa, adv[dt]);
+      __builtin_amdgcn_s_setprio(0);
+      adv[4] = MFMA16(tr_frag_5th(dbase), pa, adv[4]);
+      tr_frag_x4(qbase, bfr);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) adk[dt] = MFMA16(bfr[dt], dsa, adk[dt]);
+      __builtin_amdgcn_s_setprio(0);
+      adk[4] = MFMA16(tr_frag_5th(qbase), dsa, adk[4]);
+    }
+    // transposed tiles again: lane = key lo, d = 16dt + 4hi + r
+    if (sok) {
+      bf16* dkp = head_ptr(dk, dk_s, bh, H) + (int64_t)(s0 + lo) * dk_s.l + 4 * hi;
+      bf16* dvp = head_ptr(dv, dv_s, bh, H) + (int64_t)(s0 + lo) * dv_s.l + 4 * hi;
+#pragma unroll
+      for (int dt = 0; dt < 5; ++dt) {
+        if (dt == 4 && !tail_ok) continue;  // d >= Dr: the next head's columns
+        bf16x4 pk, pv;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          pk[r] = f2bfs(adk[dt][r]);
+          pv[r] = f2bfs(adv[dt][r]);
+        }
+        *reinterpret_cast<bf16x4*>(dkp + 16 * dt) = pk;
+        *reinterpret_cast<bf16x4*>(dvp + 16 * dt) = pv;
+      }
+    }
+  }
+}
+#endif
+
 }  // namespace
 
 // Launch of the DROP instantiations (non-causal; resident inside the resident
@@ -1191,21 +1482,41 @@ void attn_bwd_fused(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Te
   TORCH_CHECK(path == "auto" || path == "tiled" || path == "resident",
               "attn_bwd_fused: path must be auto, tiled or resident, got ", path);
   const bool aligned = res_aligned({&q, &k, &v, &o, &dO, &dq, &dk, &dv});
-  const bool resident_ok = Dr == 64 && Lq == Lk && !causal && Lk >= RES_LMIN &&
-                           Lk <= RES_LMAX && aligned;
-  TORCH_CHECK(path != "resident" || resident_ok,
-              "attn_bwd_fused: path=resident needs D == 64, Lq == Lk, non-causal, ",
-              RES_LMIN, " <= L <= ", RES_LMAX, " and 16-byte aligned rows; got D=", Dr,
-              " Lq=", Lq, " Lk=", Lk, " causal=", causal, " aligned=", aligned);
   // attention-probability dropout: t8 == 0 is today's path, untouched
   const unsigned t8 = attn_drop_threshold(p);
+  // D = 72 and 80 have a resident kernel of their own, without a dropout form
+  const bool res80 = (Dr == 72 || Dr == 80) && t8 == 0;
+  const bool resident_ok = (Dr == 64 || res80) && Lq == Lk && !causal && Lk >= RES_LMIN &&
+                           Lk <= RES_LMAX && aligned;
+  TORCH_CHECK(path != "resident" || resident_ok,
+              "attn_bwd_fused: path=resident needs D in {64, 72, 80} (no dropout at 72 and "
+              "80), Lq == Lk, non-causal, ", RES_LMIN, " <= L <= ", RES_LMAX,
+              " and 16-byte aligned rows; got D=", Dr, " Lq=", Lq, " Lk=", Lk,
+              " causal=", causal, " aligned=", aligned, " p=", p);
   check_attn_drop("attn_bwd_fused", t8, causal, Lq, Lk);
   if (t8 > 0) {
-    attn_bwd_drop(q, k, v, o, dO, lse, dq, dk, dv, scale, path != "tiled" && resident_ok,
+    attn_bwd_drop(q, k, v, o, dO, lse, dq, dk, dv, scale,
+                  path != "tiled" && resident_ok && Dr == 64,
                   make_attn_drop_args(t8, rng, site, q));
     return;
   }
-  if (path != "tiled" && resident_ok) {
+  // D = 72 / 80: auto takes the resident kernel over its whole domain, as at
+  // D = 64 (2.53-2.82x ahead of the tiled trio at every measured (D, L):
+  // profiles/attn_resident_d80_NOTES.md)
+  if (path != "tiled" && resident_ok && res80) {
+    const int LP = (Lk + 31) & ~31;
+    const size_t rshmem =
+        (size_t)2 * LP * RES80_D * sizeof(short) + (size_t)2 * LP * sizeof(float);
+    constexpr size_t rshmem_max =
+        (size_t)2 * RES_LMAX * RES80_D * sizeof(short) + (size_t)2 * RES_LMAX * sizeof(float);
+    launch_lds<attn_bwd_resident80_kernel>(
+        dim3(BH), dim3(LP / 32 * WAVE), rshmem, rshmem_max, stream, bf16_ptr(q), bf16_ptr(k),
+        bf16_ptr(v), bf16_ptr(o), bf16_ptr(dO), lse.data_ptr<float>(), bf16_ptr(dq),
+        bf16_ptr(dk), bf16_ptr(dv), Lk, Dr, (float)scale, H, hstrides(q), hstrides(k),
+        hstrides(v), hstrides(o), hstrides(dO), hstrides(dq), hstrides(dk), hstrides(dv));
+    return;
+  }
+  if (path != "tiled" && resident_ok && Dr == 64) {
     // one wave per 32 rows (two 16-row strips each); two images + lse + delta
     const int LP = (Lk + 31) & ~31;
     const size_t rshmem = (size_t)2 * LP * 64 * sizeof(short) + (size_t)2 * LP * sizeof(float);

@@ -142,8 +142,9 @@ __device__ __forceinline__ T* head_ptr(T* base, const hstride& s, int64_t bh, in
 
 // ---- attention: resident kernels (one workgroup per head) --------------------
 
-// Domain of the resident forward and backward: D = 64, Lq == Lk = L,
-// non-causal, RES_LMIN <= L <= RES_LMAX, res_aligned views (host section).
+// Domain of the resident forward and backward: D in {64, 72, 80} (72 and 80
+// without dropout), Lq == Lk = L, non-causal, RES_LMIN <= L <= RES_LMAX,
+// res_aligned views (host section).
 constexpr int RES_LMIN = 81;
 constexpr int RES_LMAX = 256;
 
@@ -153,6 +154,31 @@ constexpr int RES_LMAX = 256;
 // as the next MFMA's fragment (attention_bwd_fused.hip, resident kernel).
 __device__ __forceinline__ int noff(int row, int d) {
   return (row >> 5) * 2048 + (d >> 4) * 512 + (row & 31) * 16 + (d & 15);
+}
+
+// The same image for head dims 72 and 80 (attn_*_resident80_kernel): FIVE 16-d
+// sub-blocks per 32-row block, 5120 B a block. Nothing inside a sub-block
+// changes, so a fifth d-tile adds no new bank pattern. Columns Dr..79 are
+// written as zeros at D = 72.
+constexpr int RES80_D = 80;
+
+__device__ __forceinline__ int noff80(int row, int d) {
+  return (row >> 5) * (32 * RES80_D) + (d >> 4) * 512 + (row & 31) * 16 + (d & 15);
+}
+
+// The fifth fragment (sub-block 4) of one 32-contraction step of a noff80
+// image; `base` as given to tr_frag_x4.
+__device__ __forceinline__ bf16x8 tr_frag_5th(lds_cp base) {
+  bf16x4 al, ah;
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %2 offset:4096\n\t"
+      "ds_read_b64_tr_b16 %1, %2 offset:4608\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(al), "=&v"(ah)
+      : "v"(base)
+      : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return __builtin_shufflevector(al, ah, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // ---- fused GEMM epilogue ---------------------------------------------------
